@@ -15,7 +15,12 @@ Workload (SURVEY §8d / BASELINE.md §3): config 2 — canonical network, batch 
 non-uniform priorities.  Multi-GPU = independent replicas (own replay, own noise) that exchange
 gradient information once per step (rainbow_amd/dist.py); weak scaling (per-GPU work fixed).
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run does only what the headline figure needs: set up, warm up, time --steps steps
+(no HIP-event bracket in the timed region), write --dump-outputs, print the line.
+--dump-outputs DIR: after the timed steps, what the last of them computed — the online parameters after its Adam update, the
+  per-sample loss, the pre-clip gradient norm, the sampled batch and the priorities written back — as DIR/<name>.npy (float32 /
+  float64, ~28 MB at the largest config).  The same arguments give the same inputs on every run (fixed seeds).
+--full adds everything else, measured as before (the bracket of the dominant kernel then sits inside the timed region):
   roofline        — the step's dominant kernel by time (chosen by a bracketed probe over every candidate),
                     timed live with HIP events on its launch stream over the timed region (rb_profile_*)
   roofline_others — every other candidate kernel, timed the same way in short passes after the timed region
@@ -23,8 +28,9 @@ Prints ONE JSON line (rank 0).  Extra objects:
   roofline_per    — the second BASELINE metric (PER samples/s: sample + update_priorities, no learner) against HBM
   cpu_baseline    — the CPU oracle (a port of the reference's algorithm: numpy replay + torch-CPU
                     learner) timed on this box's host cores on a bounded sample (rank 0, N=1 only)
-  library_source_hash — hash of the sources the loaded librainbow_hip.so was built from; must equal the tree's
---no-profile: no HIP-event bracket anywhere (the run a rocprofv3 kernel trace should see).
+  per_samples_per_s, ms_per_step_unbracketed — the PER-only loop; the same steps again without the bracket
+  library_source_hash — hash of the sources the loaded librainbow_hip.so was built from; must equal the tree's (every run)
+--no-profile (with --full): no HIP-event bracket anywhere (the run a rocprofv3 kernel trace should see).
 Runs shorter than 24 steps bracket 1 launch in ceil(steps / 3) of the dominant kernel (three samples: an event pair idles the stream for
 ≈ 13 µs — five pairs were 3.4 µs per step of a 20-step run); longer runs 1 in 8.
 """
@@ -213,8 +219,9 @@ def achieved(k, seconds):
 
 def respawn_under_torchrun(opt):
     """`python bench.py --gpus N` without a launcher: start N ranks of this script (one per GPU) under
-    torch.distributed.run on this node and hand the terminal over to it."""
+    torch.distributed.run on this node as a child process and exit with its status."""
     import socket
+    import subprocess
     n_dev = torch.cuda.device_count()
     if n_dev < (1 if opt.backend == "gloo" else opt.gpus):
         sys.exit("bench.py: --gpus %d requested but only %d GPU(s) are visible" % (opt.gpus, n_dev))
@@ -224,7 +231,7 @@ def respawn_under_torchrun(opt):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(opt.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))       # a fresh process: this one has already opened the HIP runtime (device_count)
 
 
 def time_cpu_baseline(cfg, seconds=20.0):
@@ -292,6 +299,38 @@ def time_cpu_baseline(cfg, seconds=20.0):
                        "{8,16,32,%d}-thread probe" % (k, B, cap, dt, all_threads))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, agent, mem, batch):
+    """What the last timed step computed, as a caller of Agent.learn(mem) sees it, as <path>/<name>.npy (float32; integer
+    arrays as float64, exact).  Called after drain(): the step's optimiser pass and priority write-back have run."""
+    o = mem._out[batch]          # the sampler's batch of the last step (the learner draws into these buffers)
+    p = agent.params.detach()    # (the flat parameter tensor is an autograd leaf)
+    params = torch.cat([p[off:off + int(np.prod(shape))] for _n, off, shape in agent._layout])   # padding left out
+
+    def host(t):
+        return t.detach().cpu().numpy()
+    idx = host(o["tree_idxs"])
+    out = {
+        "params": host(params),                             # the online net after the step's Adam update, layout order
+        "loss": host(agent._loss),                          # per-sample loss
+        "grad_norm": host(agent._norm_buf),                 # total gradient norm before clipping
+        "tree_idxs": idx.astype(np.float64),
+        "actions": host(o["actions"]).astype(np.float64),
+        "returns": host(o["returns"]),
+        "nonterminals": host(o["nonterminals"]),
+        "weights": host(o["weights"]),                      # importance-sampling weights
+        "priorities": mem._grab("tree")[idx],               # the sum-tree leaves the step wrote back
+    }
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs of %d bytes exceed the dump limit" % total
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -311,7 +350,14 @@ def main():
                          "rank per device): same respawn, barriers, MAX-reduced elapsed and value arithmetic; the replica exchange "
                          "stages its blocks through the host.  Its number says nothing about scaling")
     ap.add_argument("--extra-tags", default="", help="comma-separated extra profiling tags to time (bytes unknown: time only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline objects, the unbracketed re-run, PER-only "
+                         "throughput, the CPU baseline (--roofline-kernel, --extra-tags, --no-profile and --no-cpu-baseline apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
     opt = ap.parse_args()
+    if not opt.full and (opt.extra_tags or opt.roofline_kernel != "auto"):
+        ap.error("--roofline-kernel and --extra-tags need --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if opt.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -386,7 +432,7 @@ def main():
                         implicit_sigma=getattr(agent, "_implicit_sigma", False))
     # the kernel the roofline object reports = the step's DOMINANT kernel by time, found by a short bracketed pass over
     # every candidate before the timed region (or forced with --roofline-kernel)
-    if opt.no_profile:
+    if opt.no_profile or not opt.full:
         kname = None
     elif opt.roofline_kernel in ktab:
         kname = opt.roofline_kernel
@@ -418,6 +464,43 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else dev)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if opt.dump_outputs and rank == 0:
+        dump_outputs(opt.dump_outputs, agent, mem, cfg["batch_size"])
+    B = cfg["batch_size"]
+
+    def check_run():
+        hdr = mem._header()
+        assert hdr.last_status == 0 and mem.failed_samples() == 0, "device sampler failed"
+        assert bool(torch.isfinite(agent._loss).all()), "non-finite loss"
+        assert mem.expired_waits() == 0, "a cross-stream wait of the early draw expired during the run"
+
+    def result_line():
+        par = "single device" if world == 1 else "replicas x%d, exchange=%s" % (world, rdist.mode())
+        if world > 1 and rehearsal:
+            par += " [REHEARSAL: %d ranks on ONE GPU over gloo — control flow only, not a scaling number]" % world
+        out = {
+            "metric": "gradient-steps/sec (batch=%d, atoms=51)" % B, "value": world * opt.steps / elapsed,
+            "unit": "gradient-steps/s", "n_gpus": world, "steps": opt.steps, "warmup": opt.warmup,
+            "ms_per_step": elapsed / opt.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": opt.config, "architecture": cfg["architecture"], "batch_per_gpu": B,
+                       "global_batch": B * world, "atoms": 51, "actions": cfg["actions"], "multi_step": cfg["multi_step"],
+                       "replay_capacity_per_gpu": cfg["capacity"], "parallelism": par},
+            "full": opt.full,
+            "early_draw": "spec_draw=1" in os.environ.get("RB_OPTS", ""),     # (opt-in: only an append-free loop like this one arms it)
+            "library_source_hash": L.source_hash(lib),
+        }
+        assert out["library_source_hash"] == __graft_entry__.source_hash(), "the loaded library was not built from this tree"
+        return out
+
+    if not opt.full:
+        check_run()
+        if rank == 0:
+            print(json.dumps(result_line()))
+        if world > 1 or force_dist:
+            torch.distributed.destroy_process_group()
+        return
+    # --full from here on
     # the same number of steps WITHOUT the event pair around the dominant kernel (what the bracketing itself costs)
     torch.cuda.synchronize(dev)
     t_plain = time.perf_counter()
@@ -441,13 +524,10 @@ def main():
     lib.rb_profile_overhead(torch.cuda.current_stream(dev).cuda_stream, 256, C.byref(ev_ms))
     ev_us = ev_ms.value * 1e3          # what an EMPTY event pair reads: reported, not subtracted (rocprof's duration of
                                        # the same kernel sits between avg_us and avg_us - event_pair_overhead_us)
-    hdr = mem._header()
-    assert hdr.last_status == 0 and mem.failed_samples() == 0, "device sampler failed"
-    assert bool(torch.isfinite(agent._loss).all()), "non-finite loss"
+    check_run()
 
     # PER-only throughput (sample + priority update, no learner), same replay
     per_iters = 500
-    B = cfg["batch_size"]
     fake_loss = torch.rand(B, device=dev) + 0.1
     # (donate=True: this loop never modifies its loss tensor between the call and the next draw, so the write-back reads it in place;
     # the DEFAULT copies caller-owned device operands at the call, like the reference's immediate update — both are timed and
@@ -469,24 +549,8 @@ def main():
     assert mem.expired_waits() == 0, "a cross-stream wait of the early draw expired during the run"
 
     if rank == 0:
-        ms_per_step = elapsed / opt.steps * 1e3
-        par = "single device" if world == 1 else "replicas x%d, exchange=%s" % (world, rdist.mode())
-        if world > 1 and rehearsal:
-            par += " [REHEARSAL: %d ranks on ONE GPU over gloo — control flow only, not a scaling number]" % world
-        out = {
-            "metric": "gradient-steps/sec (batch=%d, atoms=51)" % B, "value": world * opt.steps / elapsed,
-            "unit": "gradient-steps/s", "n_gpus": world, "steps": opt.steps, "warmup": opt.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": opt.config, "architecture": cfg["architecture"], "batch_per_gpu": B,
-                       "global_batch": B * world, "atoms": 51, "actions": cfg["actions"], "multi_step": cfg["multi_step"],
-                       "replay_capacity_per_gpu": cfg["capacity"], "parallelism": par},
-            "per_samples_per_s": per_rate * world,
-            "early_draw": "spec_draw=1" in os.environ.get("RB_OPTS", ""),     # (opt-in: only an append-free loop like this one arms it)
-            "ms_per_step_unbracketed": plain_ms,
-            "library_source_hash": L.source_hash(lib),
-        }
-        assert out["library_source_hash"] == __graft_entry__.source_hash(), "the loaded library was not built from this tree"
+        out = result_line()
+        out.update(per_samples_per_s=per_rate * world, ms_per_step_unbracketed=plain_ms)
         # the second BASELINE metric (memory.py:148-159: sample(B) + update_priorities, no learner), priced against HBM with
         # SURVEY 8(d)'s algorithmic bytes — (h + n) frames read + 2h frames written per sample — and against what actually
         # bounds it at one batch in flight: a chain of DEPENDENT round trips (sampler: tree top in LDS, 2 trips below it,

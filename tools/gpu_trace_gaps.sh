@@ -1,17 +1,17 @@
 # usage: bash tools/gpu_trace_gaps.sh <config>: rocprofv3 kernel trace of a short bench run; per kernel of the learn step the
 # mean duration and the mean idle gap between the previous kernel's end and its start (steady-state steps only).
-# bench.py runs with --no-profile: a bracketed launch (HIP event records = system-scope barrier packets) shows ~6 us of idle
-# GPU on both sides, and the LAST steps of a default bench run are its bracketed roofline_others passes (round 2 read those
-# as 'two idle gaps at the sampler launch': the sampler was simply the last tag bracketed)
+# bench.py runs with --full (its PER-only phase is summarised too) and --no-profile: a bracketed launch (HIP event records =
+# system-scope barrier packets) shows ~6 us of idle GPU on both sides, and the LAST steps of a --full bench run are its bracketed
+# roofline_others passes (round 2 read those as 'two idle gaps at the sampler launch': the sampler was simply the last tag bracketed)
 CFG=$1
-mkdir -p gpurun_out
 export TMPDIR=/tmp
 ROOT=$PWD
-cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $ROOT/gpurun_out/gaps -o gaps -- python $ROOT/bench.py --config $CFG --steps 60 --warmup 20 --no-cpu-baseline --no-profile > $ROOT/gpurun_out/gaps.log 2>&1
+TRACE=$(mktemp -d)      # the trace and the bench log, removed at the end
+cd $TRACE && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $TRACE/gaps -o gaps -- python $ROOT/bench.py --config $CFG --steps 60 --warmup 20 --full --no-cpu-baseline --no-profile > $TRACE/gaps.log 2>&1
 cd $ROOT
-python - <<'PY'
-import csv, glob, collections
-f = glob.glob("gpurun_out/gaps/**/*kernel_trace.csv", recursive=True)[0]
+TRACE=$TRACE python - <<'PY'
+import csv, glob, collections, os
+f = glob.glob(os.path.join(os.environ["TRACE"], "gaps", "**", "*kernel_trace.csv"), recursive=True)[0]
 rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
 # the timed region: the last 40 k_head launches delimit steps (one per learn call; the optimiser pass may be hosted by the
 # sampler launch, RB_LEARNER_DEFER_UPDATE, so k_clip_adam is not a per-step launch any more)
@@ -43,4 +43,4 @@ for i in range(hi - 15, hi + 1):
     r = rows[i]
     print({k: r[k] for k in r if k in ("Queue_Id", "Stream_Id", "Thread_Id", "Dispatch_Id", "Agent_Id", "Correlation_Id", "Private_Segment_Size", "LDS_Block_Size", "Scratch_Size")}, r["Kernel_Name"][:30])
 PY
-rm -rf gpurun_out/gaps
+rm -rf $TRACE
