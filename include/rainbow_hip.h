@@ -107,6 +107,16 @@ typedef struct {
  * capacity must be even and >= 2 (odd capacities crash the reference). */
 int rb_replay_create(rb_replay_t** out, int64_t capacity, int32_t history, int32_t multi_step,
                      double discount, double priority_exponent, uint64_t seed);
+/* The same replay holding S interleaved environment streams (1 <= S <= 64; S = 1 is rb_replay_create's replay): one ring, one
+ * sum tree, stream s owns the slots s, s + S, s + 2S, ...  Windows, n-step returns, the validity test of the sampler and the
+ * validation stacks follow the stream's own slots (stride S); IS weights count every stored transition (memory.py:152).
+ * Refused with RB_ERR_INVALID and a message: S outside [1, 64], capacity not a multiple of S, capacity <= (history +
+ * multi_step) * S.  Such a replay is filled by whole rounds (rb_replay_append_streams, or rb_replay_append_batch with a
+ * multiple of S transitions already in ring order); rb_replay_append refuses it.                                         */
+int rb_replay_create_streams(rb_replay_t** out, int64_t capacity, int32_t history, int32_t multi_step, double discount,
+                             double priority_exponent, uint64_t seed, int32_t streams);
+/* The stream count S of a replay (1 for rb_replay_create's). */
+int rb_replay_streams(rb_replay_t* r, int32_t* streams_host);
 int rb_replay_destroy(rb_replay_t* r);
 int rb_replay_buffers(rb_replay_t* r, rb_replay_buffers_t* out_host);
 /* synchronises `stream`, then copies the header to host */
@@ -133,6 +143,14 @@ int rb_replay_append(rb_replay_t* r, const float* state_dev, int32_t timestep, i
 int rb_replay_append_batch(rb_replay_t* r, const uint8_t* frames_dev, const int32_t* timesteps_dev,
                            const int32_t* actions_dev, const float* rewards_dev,
                            const uint8_t* nonterminals_dev, int64_t n, rb_stream_t stream);
+
+/* One append ROUND of an S-stream replay: ReplayMemory.append (memory.py:105-108) for streams 0 .. S-1 in that order, in ONE
+ * launch.  states_dev: f32 [S][history][84][84] (16-byte aligned; what rb_learner_act_batch just consumed), state[s][history-1]
+ * quantised as rb_replay_append does.  timesteps_host, actions_host, rewards_host, nonterminals_host: S values each, host
+ * memory, passed to the kernel by value — asynchronous, and the arrays may be reused as soon as the call returns.  Ring,
+ * tree and header end bit-identical to S sequential appends.  The write head must be at a round boundary (a multiple of S). */
+int rb_replay_append_streams(rb_replay_t* r, const float* states_dev, const int32_t* timesteps_host, const int32_t* actions_host,
+                             const float* rewards_host, const uint8_t* nonterminals_host, rb_stream_t stream);
 
 /* SegmentTree.find (memory.py:64-82): float64 values against float32 nodes.       */
 int rb_replay_find(rb_replay_t* r, const double* values_dev, int32_t n, float* probs_dev,
@@ -214,7 +232,7 @@ int rb_replay_update_sample(rb_replay_t* r, const int64_t* upd_tree_idx_dev, con
                             float* weights_dev, rb_stream_t stream);
 
 /* ReplayMemory.__next__ (memory.py:167-178): blanked history stack for data index i,
- * as f32 /255, out_dev f32[history][7056].                                          */
+ * as f32 /255, out_dev f32[history][7056].  With S streams: slots i - (history-1-t) S, t = 0..history-1. */
 int rb_replay_state_at(rb_replay_t* r, int64_t data_index, float* out_dev, rb_stream_t stream);
 
 /* The same for n data indices in ONE launch (the validation pass of test.py:38-39 walks the whole validation memory):

@@ -65,12 +65,15 @@ SIGNATURES = {
     "rb_profile_overhead": (c_int, [c_void_p, c_int32, C.POINTER(c_double)]),
     "rb_debug_check_guards": (c_int, [C.POINTER(c_int64), C.POINTER(c_int64)]),
     "rb_replay_create": (c_int, [C.POINTER(c_void_p), c_int64, c_int32, c_int32, c_double, c_double, c_uint64]),
+    "rb_replay_create_streams": (c_int, [C.POINTER(c_void_p), c_int64, c_int32, c_int32, c_double, c_double, c_uint64, c_int32]),
+    "rb_replay_streams": (c_int, [c_void_p, C.POINTER(c_int32)]),
     "rb_replay_destroy": (c_int, [c_void_p]),
     "rb_replay_buffers": (c_int, [c_void_p, C.POINTER(ReplayBuffers)]),
     "rb_replay_header": (c_int, [c_void_p, C.POINTER(ReplayHeader), c_void_p]),
     "rb_frame_preprocess": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "rb_replay_append": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_int32, c_void_p]),
     "rb_replay_append_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "rb_replay_append_streams": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rb_replay_find": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rb_replay_sample": (c_int, [c_void_p, c_int32, c_double, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -27,6 +27,7 @@ struct rb_replay {
   int64_t capacity;
   int32_t history, n;
   int32_t levels;       // L = depth of the leaf level
+  int32_t streams;      // S interleaved environment streams (1 = the reference's single sequential stream)
   int64_t tree_start;   // 2^L - 1
   int64_t tree_len;     // tree_start + capacity
   double omega;         // priority exponent (memory.py:99)
@@ -83,7 +84,7 @@ static int spec_join(rb_replay* r) {
 
 static ReplayView view_of(const rb_replay* r) {
   ReplayView v;
-  v.capacity = r->capacity; v.history = r->history; v.n = r->n; v.levels = r->levels;
+  v.capacity = r->capacity; v.history = r->history; v.n = r->n; v.levels = r->levels; v.streams = r->streams;
   v.tree_start = r->tree_start; v.tree_len = r->tree_len;
   v.tree = r->tree; v.frames = r->frames; v.timestep = r->timestep; v.action = r->action;
   v.reward = r->reward; v.nonterminal = r->nonterminal; v.hdr = r->hdr;
@@ -141,6 +142,89 @@ __global__ __launch_bounds__(256) void k_append_one(ReplayView v, const float* l
     if (next == 0) v.hdr->full = 1;      // memory.py:60
     v.hdr->total = v.tree[0];
     // memory.py:54,61: max(value, max) with value == max — unchanged
+  }
+}
+
+// ---------------------------------------------------------------- append round --
+// S interleaved environment streams (rb_replay_append_streams): one ROUND appends one transition per stream, stream s into
+// ring slot start + s (start = the write head, a multiple of S: a round never wraps).  The same ring, tree and header as S
+// calls of k_append_one in stream order: every leaf gets the running max (an append never changes it, memory.py:54,61) and
+// every ancestor ends as fl32(left + right) of its final children, which is what the sequential walks leave behind.
+// Blocks [0, S) quantise state[s][h-1] of stream s (f32 x 255, truncation: k_append_one's arithmetic) with 16-byte lanes;
+// block S writes the columns and the leaves and rebuilds the ancestors.  The leaves of a round are CONTIGUOUS, so on every
+// level the touched nodes form one range, and the only untouched nodes a level reads are the outside siblings at its two
+// ends: block S requests all of them in one batch of loads, then walks the L levels in LDS (one barrier per level) — one
+// round trip to memory instead of L dependent ones.  Per-stream scalars come by value in the argument block (no staging).
+#define RB_MAX_STREAMS 64
+struct AppendRound {
+  int32_t timestep[RB_MAX_STREAMS];
+  int32_t action[RB_MAX_STREAMS];
+  float reward[RB_MAX_STREAMS];
+  uint8_t nonterminal[RB_MAX_STREAMS];
+};
+__device__ __forceinline__ uint32_t rb_quant4(float4 f) {
+  // state[-1].mul(255).to(uint8) (memory.py:106), byte by byte as k_append_one
+  const uint32_t q0 = (uint32_t)(int32_t)__fmul_rn(f.x, 255.0f) & 0xFFu;
+  const uint32_t q1 = (uint32_t)(int32_t)__fmul_rn(f.y, 255.0f) & 0xFFu;
+  const uint32_t q2 = (uint32_t)(int32_t)__fmul_rn(f.z, 255.0f) & 0xFFu;
+  const uint32_t q3 = (uint32_t)(int32_t)__fmul_rn(f.w, 255.0f) & 0xFFu;
+  return q0 | (q1 << 8) | (q2 << 16) | (q3 << 24);
+}
+__global__ __launch_bounds__(256) void k_append_streams(ReplayView v, const float* states, int64_t start, AppendRound a) {
+  const int S = v.streams;
+  const int t = (int)threadIdx.x;
+  if ((int)blockIdx.x < S) {
+    const int s = (int)blockIdx.x;
+    const float4* src = (const float4*)(states + ((int64_t)s * v.history + (v.history - 1)) * RB_FRAME_BYTES);
+    uint4* dst = (uint4*)(v.frames + (start + s) * RB_FRAME_BYTES);
+    for (int w = t; w < RB_FRAME_BYTES / 16; w += (int)blockDim.x) {
+      const float4 f0 = src[4 * w], f1 = src[4 * w + 1], f2 = src[4 * w + 2], f3 = src[4 * w + 3];
+      dst[w] = make_uint4(rb_quant4(f0), rb_quant4(f1), rb_quant4(f2), rb_quant4(f3));
+    }
+    return;
+  }
+  __shared__ float s_val[2][RB_MAX_STREAMS + 2];     // values of the touched range of the current / next level
+  __shared__ float s_out[RB_MAX_LEVELS][2];          // per level: the untouched sibling left of the range, right of it
+  const int L = v.levels;
+  const int64_t leaf0 = v.tree_start + start;
+  if (t < S) {
+    const int64_t idx = start + t;
+    v.timestep[idx] = a.timestep[t];                  // memory.py:107 (the stream's own episode timestep)
+    v.action[idx] = a.action[t];
+    v.reward[idx] = a.reward[t];
+    v.nonterminal[idx] = a.nonterminal[t] ? 1 : 0;
+    const float prio = v.hdr->max;                    // memory.py:107
+    v.tree[leaf0 + t] = prio;
+    s_val[0][t] = prio;
+  } else if (t >= 64 && t < 64 + L) {                 // one lane per level: that level's outside siblings (one batch of loads)
+    const int lv = t - 64;
+    int64_t lo = leaf0, hi = leaf0 + S - 1;
+    for (int k = 0; k < lv; ++k) { lo = (lo - 1) / 2; hi = (hi - 1) / 2; }
+    s_out[lv][0] = (lo & 1) ? 0.0f : v.tree[lo - 1];  // lo a right child (even): its left sibling is outside the range
+    s_out[lv][1] = (hi & 1) ? v.tree[hi + 1] : 0.0f;  // hi a left child (odd): its right sibling is outside
+  }
+  __syncthreads();
+  int64_t lo = leaf0, hi = leaf0 + S - 1;
+  int cur = 0;
+  for (int lv = 0; lv < L; ++lv) {                   // memory.py:36-41 for every touched parent, bottom-up
+    const int64_t plo = (lo - 1) / 2, phi = (hi - 1) / 2;
+    if (t <= (int)(phi - plo)) {
+      const int64_t p = plo + t;
+      const int64_t l = 2 * p + 1, r = l + 1;
+      const float lvv = l < lo ? s_out[lv][0] : s_val[cur][l - lo];
+      const float rvv = r > hi ? s_out[lv][1] : s_val[cur][r - lo];
+      const float x = __fadd_rn(lvv, rvv);           // memory.py:25
+      s_val[cur ^ 1][t] = x;
+      v.tree[p] = x;
+    }
+    __syncthreads();
+    lo = plo; hi = phi; cur ^= 1;
+  }
+  if (t == 0) {
+    const int64_t next = start + S == v.capacity ? 0 : start + S;
+    v.hdr->index = next;                              // memory.py:59
+    if (next == 0) v.hdr->full = 1;                   // memory.py:60
+    v.hdr->total = s_val[cur][0];                     // the root
   }
 }
 
@@ -438,23 +522,27 @@ __device__ __forceinline__ float rb_sample_window(const ReplayView& v, int64_t i
   // ring slots as 32-bit, wrapped with two selects (capacity > window, checked by the host; |offset| < capacity): the
   // 64-bit while-loop form put control flow between the loads, and every load became its own ~0.35 us round trip
   // (5.8 us for the 16 loads of n = 3, 16.8 us for the 48 loads of n = 20 — measured with in-kernel timestamps)
+  // S interleaved streams (rb_replay_create_streams): window slot k of the sample is ring slot idx + k S — the same stream, k
+  // transitions later.  The create-time check (h + n) S < C keeps every offset below C in magnitude, so the two selects still wrap.
   const int32_t C = (int32_t)v.capacity;
+  const int32_t S = v.streams;
   const int32_t id = (int32_t)idx;
   const int h = v.history, n = v.n;
   const int win_len = h + n;
   auto wrap = [C](int32_t x) { x += x < 0 ? C : 0; x -= x >= C ? C : 0; return x; };
+  const int32_t first = id - (h - 1) * S;                             // window slot 0 (unwrapped)
   constexpr int NT = 8 * NCH;
   int ts[NT];
   float rw[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const int tc = t < win_len ? t : win_len - 1;
-    ts[t] = v.timestep[wrap(id + tc - (h - 1))];
+    ts[t] = v.timestep[wrap(first + tc * S)];
     const int kc = t < n ? t : n - 1;
-    rw[t] = v.reward[wrap(id + kc)];
+    rw[t] = v.reward[wrap(id + kc * S)];
   }
   const int act_now = v.action[id];                                   // slot h-1 is never blanked
-  const uint8_t nt_last = v.nonterminal[wrap(id + n)];
+  const uint8_t nt_last = v.nonterminal[wrap(id + n * S)];
   // IS weight while those loads are in flight: probs / p_total ; capacity * probs ; ** -beta (memory.py:151-153).  The
   // reference evaluates the power in float32 (numpy: ~1 ulp, machine dependent); here exp(-beta * log(x)) in float64
   // (relative error ~1e-15, then ONE rounding to float32 — correctly rounded except on near-ties) — a third of the
@@ -479,7 +567,7 @@ __device__ __forceinline__ float rb_sample_window(const ReplayView& v, int64_t i
     const bool b = ((blank >> (t - 1)) & 1ull) || ((first_bits >> t) & 1ull);
     if (b) blank |= 1ull << t;
   }
-  for (int t = 0; t < win_len; ++t) my_win[t] = ((blank >> t) & 1ull) ? -1 : wrap(id + t - (h - 1));
+  for (int t = 0; t < win_len; ++t) my_win[t] = ((blank >> t) & 1ull) ? -1 : wrap(first + t * S);
   *action_out = (int64_t)act_now;                                     // memory.py:140
   float R = 0.0f;                                                     // memory.py:142-143, k ascending
 #pragma unroll
@@ -619,6 +707,11 @@ __device__ __forceinline__ void rb_sample_main(const ReplayView& v, int32_t batc
   const int32_t full = v.hdr->full;
   const uint64_t rng_base = v.hdr->rng_counter;
   const float p_total_g = v.tree[0];
+  // Validity of slot idx (memory.py:131) per stream, without a division: with S streams the write head is J S and idx = j S + s,
+  // and the rule is (J - j) mod Cs > n and (j - J) mod Cs >= h (Cs = C / S).  With d = (index - idx) mod C and e = (idx - index)
+  // mod C that is exactly  n S < d <= C - S  and  e >= h S  (d = m S - s for m = (J - j) mod Cs >= 1; m = 0 puts d in
+  // (C - S, C); e = ((j - J) mod Cs) S + s).  S = 1 gives the reference's two tests unchanged.
+  const int64_t v_near = (int64_t)n * v.streams, v_far = C - v.streams, v_hist = (int64_t)h * v.streams;
   if (lds_top) __syncthreads();
   RB_STAMP_AT(1);
   const float p_top0 = s_top[0];                                // (an unconditional LDS read: as an operand of the select below the
@@ -648,9 +741,9 @@ __device__ __forceinline__ void rb_sample_main(const ReplayView& v, int32_t batc
       leaf = lds_top ? rb_tree_descend_fast(v.tree, s_top, n_cached, v.levels, v.tree_len, sample, &prob)
                      : rb_tree_descend_global<(MAXT <= 256 ? 6 : 4)>(v.tree, v.levels, v.tree_len, sample, &prob);   // memory.py:130
       const int64_t idx = leaf - v.tree_start;
-      // memory.py:131
-      valid = (rb_wrap(w_index, -idx, C) > (int64_t)n) && (rb_wrap(idx, -w_index, C) >= (int64_t)h) &&
-              (prob != 0.0f);
+      // memory.py:131, per stream (see v_far above): with S = 1 the second bound is d <= C - 1, always true
+      const int64_t d = rb_wrap(w_index, -idx, C);
+      valid = (d > v_near) && (d <= v_far) && (rb_wrap(idx, -w_index, C) >= v_hist) && (prob != 0.0f);
     }
     RB_STAMP_AT(2);
     ok = rb_block_all(valid, s_flag);
@@ -743,6 +836,8 @@ __device__ __forceinline__ int rb_poll_epoch(const unsigned* flag, unsigned epoc
 }
 // Frame-stack gather (memory.py:136-138 minus the /255): block = (sample, stack slot),
 // 441 sixteen-byte lanes per 7056-byte frame, zero fill for blanked slots.
+// Stream-agnostic: the ring slot of every frame comes from the sampler's window table, which already holds the stream's
+// stride (rb_sample_window); the learner's zero-copy conv path reads the ring through the same table.
 __global__ __launch_bounds__(256) void k_gather_stacks(ReplayView v, int32_t batch, const int32_t* win,
                                                         uint8_t* states, uint8_t* next_states) {
   constexpr int VEC = RB_FRAME_BYTES / 16;
@@ -854,14 +949,16 @@ __global__ __launch_bounds__(256) void k_update_sample(ReplayView v, const int64
 // -------------------------------------------------------------- validation view --
 // ReplayMemory.__next__ (memory.py:167-178): history stack ending at data index i.
 // NOTE the reference indexes data[i-h+1 .. i] with numpy negative wrap-around, not % C.
+// With S interleaved streams the stack is the slot's own stream: slots i - (h-1-t) S (mod C), t = 0..h-1.
 __global__ __launch_bounds__(256) void k_state_at(ReplayView v, int64_t data_index, float* out) {
   __shared__ int s_blank[64];
   const int h = v.history;
+  const int64_t S = v.streams;
   if (threadIdx.x == 0) {
     int blank_next = 0;
     s_blank[h - 1] = 0;
     for (int t = h - 2; t >= 0; --t) {
-      const int64_t ring_next = rb_floor_mod(data_index - (h - 1) + (t + 1), v.capacity);
+      const int64_t ring_next = rb_floor_mod(data_index - (int64_t)(h - 2 - t) * S, v.capacity);
       const int b = blank_next || (v.timestep[ring_next] == 0);
       s_blank[t] = b;
       blank_next = b;
@@ -869,7 +966,7 @@ __global__ __launch_bounds__(256) void k_state_at(ReplayView v, int64_t data_ind
   }
   __syncthreads();
   for (int t = 0; t < h; ++t) {
-    const int64_t ring = rb_floor_mod(data_index - (h - 1) + t, v.capacity);
+    const int64_t ring = rb_floor_mod(data_index - (int64_t)(h - 1 - t) * S, v.capacity);
     const uint8_t* src = v.frames + ring * RB_FRAME_BYTES;
     float* dst = out + (int64_t)t * RB_FRAME_BYTES;
     const bool blank = s_blank[t] != 0;
@@ -883,13 +980,14 @@ __global__ __launch_bounds__(256) void k_state_at(ReplayView v, int64_t data_ind
 __global__ __launch_bounds__(256) void k_states_at(ReplayView v, const int64_t* data_index, float* out) {
   __shared__ int s_blank[64];
   const int h = v.history;
+  const int64_t S = v.streams;
   const int64_t di = data_index[blockIdx.x];
   float* o = out + (int64_t)blockIdx.x * h * RB_FRAME_BYTES;
   if (threadIdx.x == 0) {
     int blank_next = 0;
     s_blank[h - 1] = 0;
     for (int t = h - 2; t >= 0; --t) {
-      const int64_t ring_next = rb_floor_mod(di - (h - 1) + (t + 1), v.capacity);
+      const int64_t ring_next = rb_floor_mod(di - (int64_t)(h - 2 - t) * S, v.capacity);
       const int b = blank_next || (v.timestep[ring_next] == 0);
       s_blank[t] = b;
       blank_next = b;
@@ -897,7 +995,7 @@ __global__ __launch_bounds__(256) void k_states_at(ReplayView v, const int64_t* 
   }
   __syncthreads();
   for (int t = 0; t < h; ++t) {
-    const int64_t ring = rb_floor_mod(di - (h - 1) + t, v.capacity);
+    const int64_t ring = rb_floor_mod(di - (int64_t)(h - 1 - t) * S, v.capacity);
     const uint8_t* src = v.frames + ring * RB_FRAME_BYTES;
     float* dst = o + (int64_t)t * RB_FRAME_BYTES;
     const bool blank = s_blank[t] != 0;
@@ -1004,8 +1102,29 @@ int rb_replay_internal_view(rb_replay_t* r, ReplayView* view, double* omega) {
 
 extern "C" {
 
+static int create_impl(rb_replay_t** out, int64_t capacity, int32_t history, int32_t multi_step, double discount,
+                       double priority_exponent, uint64_t seed, int32_t streams);
+
 int rb_replay_create(rb_replay_t** out, int64_t capacity, int32_t history, int32_t multi_step, double discount,
                      double priority_exponent, uint64_t seed) {
+  return create_impl(out, capacity, history, multi_step, discount, priority_exponent, seed, 1);
+}
+
+int rb_replay_create_streams(rb_replay_t** out, int64_t capacity, int32_t history, int32_t multi_step, double discount,
+                             double priority_exponent, uint64_t seed, int32_t streams) {
+  if (out) *out = nullptr;
+  RB_REQUIRE(streams >= 1 && streams <= RB_MAX_STREAMS, "rb_replay_create_streams: streams must be in [1, %d], got %d",
+             RB_MAX_STREAMS, (int)streams);
+  RB_REQUIRE(capacity % streams == 0, "rb_replay_create_streams: capacity %lld is not a multiple of streams %d (a round of "
+             "appends must never wrap)", (long long)capacity, (int)streams);
+  RB_REQUIRE(history < 1 || multi_step < 1 || capacity > (int64_t)(history + multi_step) * streams,
+             "rb_replay_create_streams: capacity %lld must exceed (history + multi_step) * streams = %lld (every stream's window "
+             "must fit its share of the ring)", (long long)capacity, (long long)(history + multi_step) * streams);
+  return create_impl(out, capacity, history, multi_step, discount, priority_exponent, seed, streams);
+}
+
+static int create_impl(rb_replay_t** out, int64_t capacity, int32_t history, int32_t multi_step, double discount,
+                       double priority_exponent, uint64_t seed, int32_t streams) {
   RB_REQUIRE(out != nullptr, "rb_replay_create: out is NULL");
   RB_REQUIRE(capacity >= 2 && (capacity % 2) == 0,
              "rb_replay_create: capacity must be even and >= 2 (the reference's sum-tree walk reads past the "
@@ -1015,6 +1134,7 @@ int rb_replay_create(rb_replay_t** out, int64_t capacity, int32_t history, int32
   rb_replay* r = new (std::nothrow) rb_replay();
   if (!r) { rb_set_error("rb_replay_create: host OOM"); return RB_ERR_OOM; }
   r->capacity = capacity; r->history = history; r->n = multi_step; r->omega = priority_exponent; r->seed = seed;
+  r->streams = streams;
   int32_t L = 0;
   while (((int64_t)1 << L) < capacity) ++L;  // (capacity-1).bit_length()   memory.py:17
   r->levels = L;
@@ -1121,6 +1241,8 @@ int rb_replay_header(rb_replay_t* r, rb_replay_header_t* o, rb_stream_t stream) 
 int rb_replay_append(rb_replay_t* r, const float* state_dev, int32_t timestep, int32_t action, float reward,
                      int32_t nonterminal, rb_stream_t stream) {
   RB_REQUIRE(r && state_dev, "rb_replay_append: NULL argument");
+  RB_REQUIRE(r->streams == 1, "rb_replay_append: this replay holds %d interleaved streams: append whole rounds with "
+             "rb_replay_append_streams", (int)r->streams);
   RB_SPEC_JOIN(r);
   ++r->mutations;
   const float* last = state_dev + (int64_t)(r->history - 1) * RB_FRAME_BYTES;  // state[-1], memory.py:106
@@ -1139,6 +1261,8 @@ int rb_replay_append_batch(rb_replay_t* r, const uint8_t* frames_dev, const int3
   RB_SPEC_JOIN(r);
   ++r->mutations;
   RB_REQUIRE(n >= 0 && n <= r->capacity, "rb_replay_append_batch: n must be in [0, capacity]");
+  RB_REQUIRE(n % r->streams == 0 && r->host_index % r->streams == 0, "rb_replay_append_batch: with %d interleaved streams n "
+             "must be whole rounds (a multiple of the stream count) and the write head at a round boundary", (int)r->streams);
   if (n == 0) return RB_OK;
   const ReplayView v = view_of(r);
   const int64_t start = r->host_index;
@@ -1173,6 +1297,39 @@ int rb_replay_append_batch(rb_replay_t* r, const uint8_t* frames_dev, const int3
   RB_LAUNCH_CHECK();
   r->host_index = new_index;
   if (set_full) r->host_full = 1;
+  return RB_OK;
+}
+
+int rb_replay_append_streams(rb_replay_t* r, const float* states_dev, const int32_t* timesteps_host, const int32_t* actions_host,
+                             const float* rewards_host, const uint8_t* nonterminals_host, rb_stream_t stream) {
+  RB_REQUIRE(r && states_dev && timesteps_host && actions_host && rewards_host && nonterminals_host,
+             "rb_replay_append_streams: NULL argument");
+  RB_REQUIRE(((uintptr_t)states_dev & 15u) == 0, "rb_replay_append_streams: states_dev must be 16-byte aligned");
+  const int S = r->streams;
+  RB_REQUIRE(r->host_index % S == 0, "rb_replay_append_streams: the write head (%lld) is not at a round boundary of %d streams",
+             (long long)r->host_index, S);
+  RB_SPEC_JOIN(r);
+  ++r->mutations;
+  AppendRound a;
+  memset(&a, 0, sizeof(a));
+  for (int s = 0; s < S; ++s) {      // by value: the caller's arrays are free again when this returns
+    a.timestep[s] = timesteps_host[s];
+    a.action[s] = actions_host[s];
+    a.reward[s] = rewards_host[s];
+    a.nonterminal[s] = nonterminals_host[s] ? 1 : 0;
+  }
+  const int64_t start = r->host_index;
+  RB_LAUNCH_T("append:k_append_streams", k_append_streams, dim3((unsigned)S + 1u), dim3(256), stream, view_of(r), states_dev,
+              start, a);
+  RB_LAUNCH_CHECK();
+  r->host_index = (start + S) % r->capacity;
+  if (r->host_index == 0) r->host_full = 1;
+  return RB_OK;
+}
+
+int rb_replay_streams(rb_replay_t* r, int32_t* streams) {
+  RB_REQUIRE(r && streams, "rb_replay_streams: NULL argument");
+  *streams = r->streams;
   return RB_OK;
 }
 

@@ -7,6 +7,8 @@
 struct ReplayView {
   int64_t capacity;
   int32_t history, n, levels;
+  int32_t streams;      // S interleaved environment streams (rb_replay_create_streams): stream s owns the slots s, s + S, s + 2S, ...
+                        // (fills what was the padding in front of tree_start: the view keeps its size)
   int64_t tree_start, tree_len;
   float* tree;
   uint8_t* frames;

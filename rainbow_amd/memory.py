@@ -10,6 +10,11 @@ Two ways to consume a batch:
     Needs one D2H copy of the tree indices because the reference returns them as a numpy array.
   * `sample_device(batch_size)` — device-resident outputs (uint8 frame stacks, no sync); this is
     what rainbow_amd.agent.Agent.learn uses.
+
+Vectorised environments: `ReplayMemory(args, capacity, streams=S)` holds S interleaved environment streams in one ring and
+one sum tree (stream s owns the slots s, s + S, s + 2S, ...) and is filled a round at a time with `append_streams` — one
+transition per environment, one launch.  Sampling, priorities and IS weights are those of ONE replay over all streams; windows
+and n-step returns never cross from one stream into another.  streams=1 is the reference's replay, unchanged.
 """
 import ctypes as C
 import os
@@ -70,6 +75,7 @@ class ReplayMemory:
     _pending = None
     _stage = None
     _handle = None
+    streams = 1                 # (a pickle written before interleaved streams existed restores as one stream)
     _lazy = os.environ.get("RAINBOW_AMD_LAZY_PRIORITIES", "1") != "0"
 
     @property
@@ -89,7 +95,7 @@ class ReplayMemory:
             L.check(self._lib, self._lib.rb_replay_update_priorities(self._handle, pend[0].data_ptr(), pend[1].data_ptr(),
                                                                      int(pend[0].numel()), self._stream()))
 
-    def __init__(self, args, capacity, seed=None):
+    def __init__(self, args, capacity, seed=None, streams=1):
         self.device = torch.device(args.device)
         if self.device.type != "cuda":
             raise RuntimeError("rainbow_amd.ReplayMemory lives in HBM: args.device must be a cuda (ROCm) device, got %s"
@@ -102,19 +108,29 @@ class ReplayMemory:
         self.priority_weight = float(args.priority_weight)      # beta, annealed by the caller (main.py:161)
         self.priority_exponent = float(args.priority_exponent)
         self.t = 0                                              # episode timestep counter (memory.py:100)
+        self.streams = int(streams)
+        self.stream_t = np.zeros(self.streams, dtype=np.int32)  # the same counter per environment stream (append_streams)
         self._seed = int(seed if seed is not None else np.random.randint(0, 2 ** 31 - 1))
         self._lazy = os.environ.get("RAINBOW_AMD_LAZY_PRIORITIES", "1") != "0"
         self._pending = None
         self._stage = {}
-        self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            L.check(self._lib, self._lib.rb_replay_create(C.byref(self._h), self.capacity, self.history, self.n,
-                                                          self.discount, self.priority_exponent, self._seed))
+        self._create()
         self.transitions = _TransitionsView(self)
         self._out = {}
         self._ptr_cache = {}
         self.current_idx = 0
         self._init_beta_source()
+
+    def _create(self):
+        self._h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            if self.streams == 1:
+                rc = self._lib.rb_replay_create(C.byref(self._h), self.capacity, self.history, self.n, self.discount,
+                                                self.priority_exponent, self._seed)
+            else:
+                rc = self._lib.rb_replay_create_streams(C.byref(self._h), self.capacity, self.history, self.n, self.discount,
+                                                        self.priority_exponent, self._seed, self.streams)
+            L.check(self._lib, rc)
 
     def _init_beta_source(self):
         # -beta lives in HBM so a captured hipGraph sees main.py:161's annealing (by-value kernel arguments freeze)
@@ -166,6 +182,7 @@ class ReplayMemory:
     # ------------------------------------------------------------------ reference API
     def append(self, state, action, reward, terminal):
         """memory.py:105-108.  `state` float32 [h,84,84] in [0,1] on the device (env.py:52,77)."""
+        self._one_stream("append")
         st = state
         if st.dtype != torch.float32 or st.device != self.device or not st.is_contiguous():     # (env.py hands over exactly this)
             st = state.to(device=self.device, dtype=torch.float32).contiguous()
@@ -174,9 +191,39 @@ class ReplayMemory:
         if rc != 0:
             L.check(self._lib, rc)
         self.t = 0 if terminal else self.t + 1
+        self.stream_t[0] = self.t
+
+    def _one_stream(self, what):
+        if self.streams != 1:
+            raise RuntimeError("ReplayMemory.%s: this memory interleaves %d environment streams; append whole rounds with "
+                               "append_streams(states, actions, rewards, terminals)" % (what, self.streams))
+
+    def append_streams(self, states, actions, rewards, terminals):
+        """One round of memory.py:105-108 for every environment stream at once (one launch): `states` float32 [S,h,84,84] on
+        the device (the batch Agent.act_batch just acted on), actions / rewards / terminals length-S sequences.  Stream s
+        keeps its own episode timestep (stream_t[s]).  The same ring, tree and header as S appends in stream order."""
+        S = self.streams
+        st = states
+        if st.dtype != torch.float32 or st.device != self.device or not st.is_contiguous():
+            st = states.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(st.shape) != (S, self.history, 84, 84):
+            raise ValueError("append_streams: states must be [%d, %d, 84, 84], got %s" % (S, self.history, tuple(st.shape)))
+        terminals = np.asarray(terminals, dtype=bool).reshape(-1)
+        ac = np.ascontiguousarray(np.asarray(actions, dtype=np.int32).reshape(-1))
+        rw = np.ascontiguousarray(np.asarray(rewards, dtype=np.float32).reshape(-1))
+        if len(terminals) != S or len(ac) != S or len(rw) != S:
+            raise ValueError("append_streams: actions, rewards and terminals need %d entries each" % S)
+        ts = self.stream_t
+        nt = (~terminals).astype(np.uint8)
+        L.check(self._lib, self._lib.rb_replay_append_streams(self._h, st.data_ptr(), ts.ctypes.data, ac.ctypes.data, rw.ctypes.data,
+                                                              nt.ctypes.data, self._stream()))
+        self.stream_t = np.where(terminals, 0, ts + 1).astype(np.int32)       # memory.py:108, per stream
+        if S == 1:
+            self.t = int(self.stream_t[0])
 
     def append_batch(self, frames_u8, actions, rewards, terminals):
         """n sequential appends of already-quantised last frames (uint8 [n,84,84], device)."""
+        self._one_stream("append_batch")
         n = int(frames_u8.shape[0])
         terminals = np.asarray(terminals, dtype=bool)
         ts = np.empty(n, dtype=np.int32)
@@ -185,6 +232,7 @@ class ReplayMemory:
             ts[i] = t
             t = 0 if terminals[i] else t + 1
         self.t = t
+        self.stream_t[0] = t
         d = self.device
         fr = frames_u8.to(device=d, dtype=torch.uint8).contiguous()
         ts_d = torch.from_numpy(ts).to(d)
@@ -393,7 +441,7 @@ class ReplayMemory:
         hdr = self._header()
         meta = dict(version=1, capacity=self.capacity, history=self.history, n=self.n, discount=self.discount,
                     priority_weight=self.priority_weight, priority_exponent=self.priority_exponent, t=self.t,
-                    seed=self._seed, columns={k: spec[k][1] for k in self._COLUMNS}, header=bytes(hdr).hex())
+                    streams=self.streams, stream_t=[int(x) for x in self.stream_t], seed=self._seed, columns={k: spec[k][1] for k in self._COLUMNS}, header=bytes(hdr).hex())
         blob = json.dumps(meta).encode()
         fileobj.write(b"RBRPLY01" + struct.pack("<q", len(blob)) + blob)
         stage = np.empty(chunk_bytes, dtype=np.uint8)
@@ -418,8 +466,9 @@ class ReplayMemory:
         args = types.SimpleNamespace(device=device, history_length=meta["history"], discount=meta["discount"],
                                      multi_step=meta["n"], priority_weight=meta["priority_weight"],
                                      priority_exponent=meta["priority_exponent"])
-        mem = cls(args, meta["capacity"], seed=meta["seed"])
+        mem = cls(args, meta["capacity"], seed=meta["seed"], streams=meta.get("streams", 1))   # (older streams: one stream)
         mem.t = meta["t"]
+        mem.stream_t = np.array(meta.get("stream_t", [meta["t"]]), dtype=np.int32)
         b, spec = mem._column_spec()
         for k in cls._COLUMNS:
             ptr, nbytes = spec[k]
@@ -482,10 +531,9 @@ class ReplayMemory:
         self.__dict__.update(st)
         self.device = torch.device(self.device)
         self._lib = L.load()
-        self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            L.check(self._lib, self._lib.rb_replay_create(C.byref(self._h), self.capacity, self.history, self.n,
-                                                          self.discount, self.priority_exponent, self._seed))
+        if "stream_t" not in st:        # a pickle from before interleaved streams: one stream
+            self.stream_t = np.array([self.t], dtype=np.int32)
+        self._create()
         b = L.ReplayBuffers()
         L.check(self._lib, self._lib.rb_replay_buffers(self._h, C.byref(b)))
         for key, ptr in (("tree", b.sum_tree_dev), ("frames", b.frames_dev), ("timestep", b.timestep_dev),
