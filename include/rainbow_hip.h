@@ -152,6 +152,55 @@ int rb_replay_append_batch(rb_replay_t* r, const uint8_t* frames_dev, const int3
 int rb_replay_append_streams(rb_replay_t* r, const float* states_dev, const int32_t* timesteps_host, const int32_t* actions_host,
                              const float* rewards_host, const uint8_t* nonterminals_host, rb_stream_t stream);
 
+/* The same round with DEVICE operands, for a round that never leaves the device (actions from rb_learner_act_batch, rewards and
+ * nonterminals from a device environment such as rb_catch_step): timesteps_dev i32[S], actions_dev i32[S], rewards_dev f32[S],
+ * nonterminals_dev u8[S].  timesteps_dev is IN/OUT: the kernel stores the value it read and writes back
+ * `nonterminal ? t + 1 : 0` (memory.py:108 per stream), so the caller keeps no host copy of the episode timesteps.  The
+ * arrays are read when the launch runs (stream order), not at the call.  Same refusals as rb_replay_append_streams; ring, tree
+ * and header end bit-identical to the host-operand call with the same values.                                                */
+int rb_replay_append_streams_dev(rb_replay_t* r, const float* states_dev, int32_t* timesteps_dev, const int32_t* actions_dev,
+                                 const float* rewards_dev, const uint8_t* nonterminals_dev, rb_stream_t stream);
+
+/* ================================================================ device Catch ==
+ * A small built-in environment that lives on the device: S independent games of Catch on the 84 x 84 screen, one workgroup
+ * per stream, so that a training round (act -> step -> append) is launches on one stream with no synchronisation.
+ * Rules:
+ *  - logical grid 12 x 12, one cell = 7 x 7 pixels; the ball is 1 cell at intensity 1.0, the paddle 3 cells wide on the
+ *    bottom row (row 11) at intensity 0.5, background 0 (255, 127 and 0 after the replay's x * 255 truncation);
+ *  - actions: 0 stay, 1 left, 2 right (the paddle's left cell moves by one, clamped to [0, 9]); 3 actions; any other value
+ *    counts as stay;
+ *  - per step the paddle moves, then the ball falls one row; when the ball reaches the bottom row the episode ends with
+ *    reward +1 if its column lies under the paddle, else -1; every other step has reward 0 (an episode is 11 steps);
+ *  - episode e (0, 1, 2, ...) of stream s starts with the ball in row 0, column x0 % 12, and the paddle's left cell at
+ *    x1 % 10, where (x0, x1, ., .) = Philox4x32-10(key = seed, counter = (lo = e, hi = s)): counter-based, no stored
+ *    generator state.  rb_catch_reset starts the NEXT episode of every stream (the first call starts episode 0);
+ *  - the observation of a state is the rendered 84 x 84 frame; a frame stack is f32 [history][84][84], oldest first.
+ * stacks_* are f32 [S][history][84][84], 16-byte aligned: the layout rb_learner_act_batch and rb_replay_append_streams* take. */
+typedef struct rb_catch rb_catch_t;
+typedef struct {
+  int64_t episodes;     /* episodes finished since create / rb_catch_reset_stats, all streams */
+  int64_t catches;      /* of which the ball was caught */
+  double return_sum;    /* sum of the episode returns */
+} rb_catch_stats_t;
+#define RB_CATCH_ACTIONS 3
+/* 1 <= streams <= 64, 1 <= history <= 16. */
+int rb_catch_create(rb_catch_t** out, int32_t streams, int32_t history, uint64_t seed);
+int rb_catch_destroy(rb_catch_t* c);
+/* Every stream starts its next episode; stacks_dev gets the S reset stacks (history - 1 zero frames, then the first
+ * observation: env.py:44-52).  Asynchronous.                                                                      */
+int rb_catch_reset(rb_catch_t* c, float* stacks_dev, rb_stream_t stream);
+/* One step of every stream (one launch, asynchronous): actions_dev i32[S] in; rewards_dev f32[S], nonterminals_dev u8[S]
+ * (0 = this step ended the episode) out.  stacks_out[s] = stacks_in[s] shifted by one frame with the new observation last
+ * (env.py:70); where the step ended the episode, stacks_out[s] is instead the reset stack of the stream's next episode (what
+ * main.py:147-148 hands to the next act).  Out of place: stacks_out_dev must not overlap stacks_in_dev.  Needs a
+ * rb_catch_reset first (RB_ERR_STATE otherwise).                                                                          */
+int rb_catch_step(rb_catch_t* c, const int32_t* actions_dev, const float* stacks_in_dev, float* stacks_out_dev,
+                  float* rewards_dev, uint8_t* nonterminals_dev, rb_stream_t stream);
+/* Totals the device has accumulated (a training loop never has to synchronise to know how it is doing).  SYNCHRONISES `stream`. */
+int rb_catch_stats(rb_catch_t* c, rb_catch_stats_t* out_host, rb_stream_t stream);
+/* Zero those totals (stream-ordered, asynchronous). */
+int rb_catch_reset_stats(rb_catch_t* c, rb_stream_t stream);
+
 /* SegmentTree.find (memory.py:64-82): float64 values against float32 nodes.       */
 int rb_replay_find(rb_replay_t* r, const double* values_dev, int32_t n, float* probs_dev,
                    int64_t* data_idx_dev, int64_t* tree_idx_dev, rb_stream_t stream);

@@ -52,6 +52,11 @@ class TensorDesc(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("offset", c_int64), ("ndim", c_int32), ("shape", c_int32 * 4)]
 
 
+class CatchStats(C.Structure):
+    """rb_catch_stats_t (include/rainbow_hip.h)."""
+    _fields_ = [("episodes", c_int64), ("catches", c_int64), ("return_sum", c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/rainbow_hip.h declares
 SIGNATURES = {
     "rb_last_error": (c_char_p, []),
@@ -74,6 +79,13 @@ SIGNATURES = {
     "rb_replay_append": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_int32, c_void_p]),
     "rb_replay_append_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "rb_replay_append_streams": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rb_replay_append_streams_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rb_catch_create": (c_int, [C.POINTER(c_void_p), c_int32, c_int32, c_uint64]),
+    "rb_catch_destroy": (c_int, [c_void_p]),
+    "rb_catch_reset": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "rb_catch_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rb_catch_stats": (c_int, [c_void_p, C.POINTER(CatchStats), c_void_p]),
+    "rb_catch_reset_stats": (c_int, [c_void_p, c_void_p]),
     "rb_replay_find": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rb_replay_sample": (c_int, [c_void_p, c_int32, c_double, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -368,13 +368,26 @@ class Agent:
         self._forward_single(state)
         return int(self._aq_act[0])
 
-    def act_batch(self, states):
+    def act_batch(self, states, device_out=False):
         """Vectorised actors: `states` f32 [n, h, 84, 84] on the device (processed 2*batch_size at a time).
-        Returns the n greedy actions (numpy int64), i.e. [self.act(s) for s in states] in one forward."""
+        Returns the n greedy actions (numpy int64), i.e. [self.act(s) for s in states] in one forward.
+        device_out=True: the actions stay on the device — an int32 [n] tensor, final in stream order — and the call does NOT
+        synchronise (for an environment that lives on the device: rainbow_amd.envs, ReplayMemory.append_streams)."""
         self._flush_noise()
-        st = states.to(device=self.device, dtype=torch.float32).contiguous()
+        st = states
+        if st.dtype != torch.float32 or st.device != self.device or not st.is_contiguous():
+            st = states.to(device=self.device, dtype=torch.float32).contiguous()
         n = int(st.shape[0])
         cap = int(self._act_np.shape[0])          # 2 * batch_size images fit the learner's activation buffers
+        if device_out:
+            acts = torch.empty(n, dtype=torch.int32, device=self.device)
+            for lo in range(0, n, cap):
+                m = min(cap, n - lo)
+                rc = self._lib.rb_learner_act_batch(self._h, st[lo:lo + m].data_ptr(), m, 1 if self.training else 0,
+                                                    acts[lo:lo + m].data_ptr(), None, self._stream())
+                if rc != 0:
+                    L.check(self._lib, rc)
+            return acts
         out = np.empty(n, dtype=np.int64)
         for lo in range(0, n, cap):
             m = min(cap, n - lo)

@@ -154,13 +154,24 @@ __global__ __launch_bounds__(256) void k_append_one(ReplayView v, const float* l
 // block S writes the columns and the leaves and rebuilds the ancestors.  The leaves of a round are CONTIGUOUS, so on every
 // level the touched nodes form one range, and the only untouched nodes a level reads are the outside siblings at its two
 // ends: block S requests all of them in one batch of loads, then walks the L levels in LDS (one barrier per level) — one
-// round trip to memory instead of L dependent ones.  Per-stream scalars come by value in the argument block (no staging).
+// round trip to memory instead of L dependent ones.  Per-stream scalars come by value in the argument block (AppendRound: host
+// operands, no staging) or from device arrays (AppendRoundDev: rb_replay_append_streams_dev, a round whose operands never
+// left the device); the kernel body is the same for both.  With device operands the timestep vector is in/out: the lane that
+// stored stream t's timestep writes back the stream's next one (memory.py:108), so the caller keeps no host copy of it.
 #define RB_MAX_STREAMS 64
 struct AppendRound {
   int32_t timestep[RB_MAX_STREAMS];
   int32_t action[RB_MAX_STREAMS];
   float reward[RB_MAX_STREAMS];
   uint8_t nonterminal[RB_MAX_STREAMS];
+  static constexpr bool kDevice = false;
+};
+struct AppendRoundDev {
+  int32_t* timestep;
+  const int32_t* action;
+  const float* reward;
+  const uint8_t* nonterminal;
+  static constexpr bool kDevice = true;
 };
 __device__ __forceinline__ uint32_t rb_quant4(float4 f) {
   // state[-1].mul(255).to(uint8) (memory.py:106), byte by byte as k_append_one
@@ -170,7 +181,8 @@ __device__ __forceinline__ uint32_t rb_quant4(float4 f) {
   const uint32_t q3 = (uint32_t)(int32_t)__fmul_rn(f.w, 255.0f) & 0xFFu;
   return q0 | (q1 << 8) | (q2 << 16) | (q3 << 24);
 }
-__global__ __launch_bounds__(256) void k_append_streams(ReplayView v, const float* states, int64_t start, AppendRound a) {
+template <class Ops>
+__global__ __launch_bounds__(256) void k_append_streams(ReplayView v, const float* states, int64_t start, Ops a) {
   const int S = v.streams;
   const int t = (int)threadIdx.x;
   if ((int)blockIdx.x < S) {
@@ -189,10 +201,13 @@ __global__ __launch_bounds__(256) void k_append_streams(ReplayView v, const floa
   const int64_t leaf0 = v.tree_start + start;
   if (t < S) {
     const int64_t idx = start + t;
-    v.timestep[idx] = a.timestep[t];                  // memory.py:107 (the stream's own episode timestep)
+    const int32_t ts = a.timestep[t];
+    const uint8_t nt = a.nonterminal[t] ? 1 : 0;
+    v.timestep[idx] = ts;                             // memory.py:107 (the stream's own episode timestep)
     v.action[idx] = a.action[t];
     v.reward[idx] = a.reward[t];
-    v.nonterminal[idx] = a.nonterminal[t] ? 1 : 0;
+    v.nonterminal[idx] = nt;
+    if constexpr (Ops::kDevice) a.timestep[t] = nt ? ts + 1 : 0;   // memory.py:108, per stream
     const float prio = v.hdr->max;                    // memory.py:107
     v.tree[leaf0 + t] = prio;
     s_val[0][t] = prio;
@@ -1319,8 +1334,29 @@ int rb_replay_append_streams(rb_replay_t* r, const float* states_dev, const int3
     a.nonterminal[s] = nonterminals_host[s] ? 1 : 0;
   }
   const int64_t start = r->host_index;
-  RB_LAUNCH_T("append:k_append_streams", k_append_streams, dim3((unsigned)S + 1u), dim3(256), stream, view_of(r), states_dev,
-              start, a);
+  RB_LAUNCH_T("append:k_append_streams", k_append_streams<AppendRound>, dim3((unsigned)S + 1u), dim3(256), stream, view_of(r),
+              states_dev, start, a);
+  RB_LAUNCH_CHECK();
+  r->host_index = (start + S) % r->capacity;
+  if (r->host_index == 0) r->host_full = 1;
+  return RB_OK;
+}
+
+int rb_replay_append_streams_dev(rb_replay_t* r, const float* states_dev, int32_t* timesteps_dev, const int32_t* actions_dev,
+                                 const float* rewards_dev, const uint8_t* nonterminals_dev, rb_stream_t stream) {
+  RB_REQUIRE(r && states_dev && timesteps_dev && actions_dev && rewards_dev && nonterminals_dev,
+             "rb_replay_append_streams_dev: NULL argument");
+  RB_REQUIRE(((uintptr_t)states_dev & 15u) == 0, "rb_replay_append_streams_dev: states_dev must be 16-byte aligned");
+  const int S = r->streams;
+  RB_REQUIRE(r->host_index % S == 0, "rb_replay_append_streams_dev: the write head (%lld) is not at a round boundary of %d streams",
+             (long long)r->host_index, S);
+  RB_SPEC_JOIN(r);
+  ++r->mutations;
+  AppendRoundDev a;
+  a.timestep = timesteps_dev; a.action = actions_dev; a.reward = rewards_dev; a.nonterminal = nonterminals_dev;
+  const int64_t start = r->host_index;
+  RB_LAUNCH_T("append:k_append_streams_dev", k_append_streams<AppendRoundDev>, dim3((unsigned)S + 1u), dim3(256), stream,
+              view_of(r), states_dev, start, a);
   RB_LAUNCH_CHECK();
   r->host_index = (start + S) % r->capacity;
   if (r->host_index == 0) r->host_full = 1;
@@ -1598,6 +1634,8 @@ int rb_u8_to_unit_f32(const uint8_t* src_dev, float* dst_dev, int64_t n, rb_stre
 }
 
 }  // extern "C"
+
+#include "vec_env.h"   // device-resident environments (rb_catch_*)
 
 // (C++ linkage: called by learner.hip flush_update, not part of the C ABI)
 int rb_launch_adam_pending(const ClipAdamArgs* args_dev, int blocks, void* stream) {

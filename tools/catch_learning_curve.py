@@ -1,0 +1,81 @@
+"""Learning curves of the device agent on the device Catch environment (a measurement, not a test): rainbow_amd with production
+randomness (device Philox sampler and noise, lazy reset_noise, deferred optimiser pass, beta annealing, target syncs — all
+defaults) through rainbow_amd.loop.train_device, with the options tests/golden/make_golden_catch.py gives the reference.
+Every --t-eval env steps the agent is evaluated in eval() mode over 256 episodes on a fresh environment with a fixed seed.
+One line per checkpoint; `--no-learn` runs the same loop with learn() skipped (what an agent that does not learn scores)."""
+import argparse
+import os
+import sys
+import time
+import types
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+EVAL_SEED = 777_001
+
+
+def options(t_max, dev):
+    return types.SimpleNamespace(
+        device=dev, architecture="data-efficient", hidden_size=256, multi_step=20, learning_rate=1e-4, replay_frequency=1,
+        target_update=2000, batch_size=32, atoms=51, V_min=-10.0, V_max=10.0, history_length=4, noisy_std=0.1, discount=0.99,
+        priority_exponent=0.5, priority_weight=0.4, adam_eps=1.5e-4, norm_clip=10.0, reward_clip=1, learn_start=1600,
+        model=None, T_max=t_max)
+
+
+def run(S, seed, t_max, t_eval, learn, dev):
+    from rainbow_amd.agent import Agent
+    from rainbow_amd.envs import CatchVec
+    from rainbow_amd.loop import evaluate_device, train_device
+    from rainbow_amd.memory import ReplayMemory
+    args = options(t_max, dev)
+    args.evaluation_interval = t_eval
+    np.random.seed(seed)
+    torch.manual_seed(np.random.randint(1, 10000))
+    env = CatchVec(S, dev, seed=seed)
+    agent = Agent(args, env)
+    cap = -(-t_max // (2 * S)) * 2 * S
+    mem = ReplayMemory(args, cap, seed=seed, streams=S)
+    if not learn:
+        agent.learn = lambda mem: None
+    curve = []
+
+    def on_eval(T):
+        ev = CatchVec(16, dev, seed=EVAL_SEED)
+        curve.append((T, evaluate_device(agent, ev, 256)))
+        ev.close()
+
+    t0 = time.perf_counter()
+    try:
+        train_device(agent, mem, env, args, t_max, on_eval=on_eval)
+        note = ""
+    except RuntimeError as e:
+        note = "  STOPPED: " + str(e)[:150]
+    torch.cuda.synchronize()
+    print("S %2d seed %3d %s (%.1f s): " % (S, seed, "learn" if learn else "NO-LEARN", time.perf_counter() - t0)
+          + " ".join("%d:%+.3f" % c for c in curve) + "  training-episode mean %+.3f" % env.stats()["mean_return"] + note,
+          flush=True)
+    env.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--t-max", type=int, default=20000)
+    ap.add_argument("--t-eval", type=int, default=2000)
+    ap.add_argument("--streams", type=int, nargs="+", default=[1, 16])
+    ap.add_argument("--seeds", type=int, default=5)
+    ap.add_argument("--no-learn", action="store_true")
+    a = ap.parse_args()
+    import __graft_entry__
+    __graft_entry__.build()
+    dev = torch.device("cuda", 0)
+    for S in a.streams:
+        for k in range(a.seeds if S == 1 else min(3, a.seeds)):
+            run(S, 101 + 7 * k, a.t_max, a.t_eval, not a.no_learn, dev)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,124 @@
+"""Host-driven round against device-resident round of the vectorised actor loop, same box, same process, interleaved A/B, for
+S in {1, 4, 16, 64} at the headline config (bench.py's pong-canonical-b32 network; 3 actions: the game's).
+
+  A (host-driven, tools/vec_loop_bench.py's shape):  Agent.act_batch -> numpy (stream synchronise) -> host environment
+     stand-in (rewards / terminals from a table) -> ReplayMemory.append_streams with host operands (by value in the launch)
+  B (device round):  Agent.act_batch(device_out=True) -> CatchVec.step_device -> append_streams with device operands
+
+Both sides launch the same Catch step kernel for their next frame stacks (A feeds it a fixed device action vector: a host
+environment would upload whole frames instead, which A is not charged for), so the difference is the per-round synchronise,
+the D2H / by-value operand marshalling and the interpreter work around them.  Measured twice: the acting round alone, and the
+whole loop with reset_noise + learn at the reference's ratio (one learn per 4 env steps).  Blocks of rounds alternate
+A, B, A, B, ...; the figure is the median block.  Prints a small table and one JSON line.  Not the headline metric (bench.py is)."""
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bench  # noqa: E402
+import vec_loop_bench  # noqa: E402
+
+REPLAY_FREQUENCY = 4
+BLOCKS = 7
+
+
+def block(fn, n, dev):
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize(dev)
+    return (time.perf_counter() - t0) / n * 1e6
+
+
+def run(S, capacity, rounds, dev):
+    from rainbow_amd import _lib as L
+    from rainbow_amd.agent import Agent
+    from rainbow_amd.envs import CatchVec
+    from rainbow_amd.memory import ReplayMemory
+    cfg = dict(bench.CONFIGS["pong-canonical-b32"])
+    args = bench.make_args(cfg, dev)
+    lib = L.load()
+    envs = {k: CatchVec(S, dev, seed=11) for k in "AB"}
+    agent = Agent(args, envs["A"])
+    mems = {k: ReplayMemory(args, capacity, seed=7, streams=S) for k in "AB"}
+    for m in mems.values():
+        vec_loop_bench.fill(m, lib, L, capacity, envs["A"].action_space(), seed=0)
+    rs = np.random.RandomState(4)
+    rewards = [rs.choice([-1.0, 0.0, 1.0], size=S) for _ in range(8)]
+    no_end = np.zeros(S, dtype=bool)
+    fixed_actions = torch.zeros(S, dtype=torch.int32, device=dev)
+    st = {k: {"stacks": envs[k].reset().reshape(S, 4, 84, 84), "k": 0, "owed": 0.0} for k in "AB"}
+
+    def learn_owed(s, mem):
+        s["owed"] += S / REPLAY_FREQUENCY
+        while s["owed"] >= 1.0:
+            agent.reset_noise()
+            agent.learn(mem)
+            s["owed"] -= 1.0
+
+    def round_a(learn):
+        s = st["A"]
+        s["k"] += 1
+        a = agent.act_batch(s["stacks"])                                   # synchronises; numpy
+        rw, te = rewards[s["k"] & 7], no_end                               # the host environment stand-in
+        nxt, _, _ = envs["A"].step_device(fixed_actions)
+        mems["A"].append_streams(s["stacks"], a, rw, te)
+        s["stacks"] = nxt
+        if learn:
+            learn_owed(s, mems["A"])
+
+    def round_b(learn):
+        s = st["B"]
+        a = agent.act_batch(s["stacks"], device_out=True)
+        nxt, rw, nt = envs["B"].step_device(a)
+        mems["B"].append_streams(s["stacks"], a, rw, nonterminals=nt)
+        s["stacks"] = nxt
+        if learn:
+            learn_owed(s, mems["B"])
+
+    out = {}
+    for learn, tag in ((False, "act_round"), (True, "loop_round")):
+        for _ in range(20):
+            round_a(learn); round_b(learn)
+        ta, tb = [], []
+        for _ in range(BLOCKS):
+            ta.append(block(lambda: round_a(learn), rounds, dev))
+            tb.append(block(lambda: round_b(learn), rounds, dev))
+        out[tag + "_host_us"], out[tag + "_device_us"] = statistics.median(ta), statistics.median(tb)
+        out[tag + "_host_spread_us"] = max(ta) - min(ta)
+        out[tag + "_device_spread_us"] = max(tb) - min(tb)
+    out["env_steps_per_s_host"] = S * 1e6 / out["loop_round_host_us"]
+    out["env_steps_per_s_device"] = S * 1e6 / out["loop_round_device_us"]
+    for e in envs.values():
+        e.close()
+    return out
+
+
+def main():
+    import __graft_entry__
+    __graft_entry__.build()
+    dev = torch.device("cuda", 0)
+    capacity = int(os.environ.get("LOOP_CAPACITY", str(1 << 17)))      # a multiple of every S measured
+    result = {"capacity": capacity, "blocks": BLOCKS}
+    print("%3s | %-34s | %-34s | env-steps/s host -> device" % ("S", "acting round us: host / device", "loop round us (+learns): host / device"))
+    for S in (1, 4, 16, 64):
+        rounds = max(40, 2000 // S)
+        r = {k: round(v, 2) for k, v in run(S, capacity, rounds, dev).items()}
+        result["S%d" % S] = r
+        print("%3d | %10.1f / %-10.1f (spread %4.1f / %4.1f) | %10.1f / %-10.1f | %9.0f -> %9.0f"
+              % (S, r["act_round_host_us"], r["act_round_device_us"], r["act_round_host_spread_us"], r["act_round_device_spread_us"],
+                 r["loop_round_host_us"], r["loop_round_device_us"], r["env_steps_per_s_host"], r["env_steps_per_s_device"]), flush=True)
+        torch.cuda.empty_cache()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
