@@ -207,7 +207,7 @@ __device__ __forceinline__ void rb_head_act_body(int Z, int A, const float* lg, 
 #else
     if (err && err_epoch != 0u && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == err_epoch) best = -1;   // a bounded in-launch wait of THIS launch expired: no action
 #endif
-#if !defined(RB_HOST_INTERP) && !defined(RB_ACT_NO_PACK)      // (RB_ACT_NO_PACK: variant build for A/B runs)
+#if !defined(RB_HOST_INTERP)
     // (action, q) as ONE aligned 8-byte word where the caller laid them out that way (rainbow_amd/agent.py _forward_single: a pinned
     // pair): a single system-scope store — both are there when the host sees the action change, and the launch ends one host-memory
     // round trip earlier than with q, a system-scope fence, then the action (round 6: ~1 us of act()'s 39)
@@ -565,12 +565,8 @@ __global__ __launch_bounds__(256) void k_act_fused(ActFusedArgs a) {
     // through).  Transitive: a producer of boundary p waited for boundary p - 1 before it produced.
     const int units = units_of(phase);
     const bool has_work = wg < units;                            // block-uniform
-#if defined(RB_ACT_ALL_ARRIVE)      // (variant build for A/B runs: every workgroup arrives and waits at every boundary)
-    if (prev >= 0) rb_fan_wait(a.ctr + prev * (RB_FAN_SHARDS * RB_FAN_STRIDE), a.epoch * (unsigned)(G / RB_FAN_SHARDS), a.err, a.epoch);
-#else
     if (prev >= 0 && has_work)
       rb_fan_wait_first(a.ctr + prev * (RB_FAN_SHARDS * RB_FAN_STRIDE), a.epoch, prev_units < G ? prev_units : G, a.err, a.epoch);
-#endif
     RB_WGT(11, wg, 1 + phase);
     if (phase < 3) {
       const ActConvArgs& c = a.conv[phase];
@@ -608,11 +604,7 @@ __global__ __launch_bounds__(256) void k_act_fused(ActFusedArgs a) {
       rb_head_act_body(a.Z, a.A, lg, a.support, s_mean, s_ev, a.action_out, a.q_out, a.err, a.epoch);
     }
     RB_WGT(10, wg, 1 + phase);
-#if defined(RB_ACT_ALL_ARRIVE)
-    if (phase + 1 < a.phase_hi) rb_fan_signal(a.ctr + phase * (RB_FAN_SHARDS * RB_FAN_STRIDE), wg);
-#else
     if (phase + 1 < a.phase_hi && has_work) rb_fan_signal(a.ctr + phase * (RB_FAN_SHARDS * RB_FAN_STRIDE), wg);
-#endif
     prev = phase; prev_units = units;
   }
 }

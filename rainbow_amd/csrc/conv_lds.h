@@ -17,9 +17,6 @@
 
 #if defined(RB_STAMP)
 extern __device__ long long g_cstamp[64];
-#ifndef RB_MSTAMP_KS
-#define RB_MSTAMP_KS 4
-#endif
 #define RB_CSTAMP(i) do { if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) g_cstamp[i] = wall_clock64(); } while (0)
 #define RB_CSTAMP_LAST(i) do { if (threadIdx.x == 0 && blockIdx.x == gridDim.x - 1 && blockIdx.y == gridDim.y - 1 && blockIdx.z == gridDim.z - 1) g_cstamp[i] = wall_clock64(); } while (0)
 // per-workgroup timeline: g_wgt[kernel id][workgroup][slot] = wall_clock64 (100 MHz) at phase boundaries, slot 7 = where
@@ -49,7 +46,7 @@ struct ConvLdsFwdArgs {
   float* out;                // [img][cout][P]
   float* out_blocked;        // optional second copy of the flattened output in the k-blocked layout of noisy_linear.h
   int rows_total;            //   ... with this many rows (images)
-  int ipb;                   // k_conv_fwd_multi: images per workgroup
+  int ipb;                   // k_conv_fwd_multi_t16 / k_conv_fwd_full: images per workgroup
   int img_fast;              // k_conv_fwd_lds: grid = (images, cout tiles, position chunks) — the image is the fastest block index
 };
 
@@ -171,11 +168,7 @@ struct ConvFwdWaves {
   // units): waves w, w + 4, w + 8 share a SIMD, so two SIMDs multiplied for three units and two for two — and with two such
   // workgroups per CU those SIMDs' MFMAs were the launch's critical path.  The last two units run instead as four half-units
   // (unit, reduction half) on four waves, one per SIMD; the halves meet through 4 KB of LDS: 2.5 units per SIMD.
-#if defined(RB_NO_SPLIT_LAST)    // (variant build for A/B runs)
-  static constexpr bool SPLIT_LAST = false;
-#else
   static constexpr bool SPLIT_LAST = T16 == 1 && PT >= 3 && ((2 * PT) % 4) == 2 && ((KMAX / 4) % 8) == 0;
-#endif
   static constexpr int TILE_WAVES = T16 == 1 ? (SPLIT_LAST ? 2 * PT + 2 : 2 * PT) : PT;
   static constexpr int PARTF = SPLIT_LAST ? 4 * 4 * 64 : 0;   // floats of LDS behind ConvFwdLdsSize::FLOATS for the half-units' partial tiles
   static constexpr int NWV = T16 == 0 ? RB_CONV_WAVES : (TILE_WAVES + 3) / 4 * 4;
@@ -715,231 +708,16 @@ void k_conv_fwd_t16(ConvLdsFwdArgs a) {
   else rb_conv_fwd_body<G, NT, PR, KMAX, FIRST, PCH, false, CTW>(a, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, smem);
 }
 
-// ---- large batches: one weight slab per workgroup, a loop over images -----------------------------------------
-// At 768 images the one-image workgroup above stages 34-76 KB of transposed weights for 2.6-5.3 us of MFMAs, 6-15 times
-// per CU.  Here a workgroup owns (position chunk, 32-channel slab) and walks a.ipb images: the slab, the tap table and
-// the epilogue's bias terms are set up once (again where the image range crosses from the online to the target net);
-// per image only the patch is staged, and the NEXT image's patch is already in flight (registers) under this image's
-// MFMA loop and reductions.  The reduction scratch has a
-// region of its own (it cannot overlay operands that live across images).
-// grid = (position chunks, cout / 32, image groups); block = 512.
-template <class G, int PR, int KMAX>
-struct ConvFwdMultiLds {
-  static constexpr int KPAD = (KMAX + 2 * RB_CONV_WAVES - 1) / (2 * RB_CONV_WAVES) * (2 * RB_CONV_WAVES);
-  static constexpr int FLOATS = KPAD * 33 + (KMAX / G::KK) * PR * G::IH + RB_CONV_WAVES * 16 * 64;
-  static constexpr bool FITS = FLOATS * 4 + KPAD * 4 <= 160 * 1024;
-};
-template <class G, int NT, int PR, int KMAX, bool FIRST, int PCH = 32 * NT>
-__global__ __launch_bounds__(RB_CONV_THREADS) void k_conv_fwd_multi(ConvLdsFwdArgs a) {
-  constexpr int KGRAN = 2 * RB_CONV_WAVES;
-  constexpr int KPAD = (KMAX + KGRAN - 1) / KGRAN * KGRAN;
-  constexpr int PLANE = PR * G::IH;                 // floats per channel in the patch
-  constexpr int CMAX = KMAX / G::KK;
-  constexpr int RED = RB_CONV_WAVES * 16 * 64;      // reduction scratch for ONE 32-position tile
-  constexpr int OPS = KPAD * 33 + CMAX * PLANE;
-  __shared__ __attribute__((aligned(16))) float s_all[OPS + RED];
-  __shared__ int s_koff[KPAD];
-  float* s_w = s_all;
-  float* s_patch = s_all + KPAD * 33;
-  float* s_red = s_all + OPS;
-
-  const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-#if defined(RB_STAMP)
-  const bool mst = G::KS == RB_MSTAMP_KS && t == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0;
-#define RB_MSTAMP(i) do { if (mst) g_cstamp[i] = wall_clock64(); } while (0)
-#else
-#define RB_MSTAMP(i) ((void)0)
-#endif
-  RB_MSTAMP(48);
-  // images [z * ipb, (z + 1) * ipb) of the whole list (net 0's first); a range that straddles the nets re-stages its slab
-  // (img_fast: grid = (image groups, cout tiles, position chunks) — a group's workgroups of consecutive layers with the same
-  // ipb share an XCD, see k_conv_fwd_lds)
-  const int img0 = (a.img_fast ? (int)blockIdx.x : (int)blockIdx.z) * a.ipb;
-  const int img_end = img0 + a.ipb < a.rows_total ? img0 + a.ipb : a.rows_total;
-  const int cout0 = (int)blockIdx.y * 32;
-  const int p0 = (a.img_fast ? (int)blockIdx.z : (int)blockIdx.x) * PCH;
-  const int cin = a.cin;
-  const int K = cin * G::KK;
-  const int oy0 = p0 / G::OH;
-  const int iy0 = oy0 * G::S;
-  int rows = G::IH - iy0;
-  if (rows > PR) rows = PR;
-  const int per_c = rows * G::IH;
-
-  // ---- once: tap table (the weight slab: at the first image and where the net changes)
-  for (int k = t; k < KPAD; k += RB_CONV_THREADS) {
-    const int kc = k < K ? k : K - 1;
-    const int c = kc / G::KK, r = kc % G::KK;
-    s_koff[k] = c * PLANE + (r / G::KS) * G::IH + (r % G::KS);
-  }
-
-  // ---- the patch of one image: loads into registers (issue), LDS stores later (commit)
-  constexpr bool VEC = !FIRST && (G::IH % 4 == 0);          // per_c, iy0 * IH and IP are then multiples of 4
-  constexpr int NU = FIRST ? 2 : 1, NV = (!FIRST && VEC) ? 8 : 1, NS = (!FIRST && !VEC) ? 12 : 1;
-  static_assert(!FIRST || CMAX * PLANE <= 16 * NU * RB_CONV_THREADS, "u8 patch fits one batch of loads");
-  static_assert(FIRST || !VEC || CMAX * PLANE <= 4 * NV * RB_CONV_THREADS, "f32 patch fits one batch of float4 loads");
-  static_assert(FIRST || VEC || CMAX * PLANE <= NS * RB_CONV_THREADS, "f32 patch fits one batch of scalar loads");
-  uint4 pu[NU];
-  float4 pv[NV];
-  float ps[NS];
-  auto issue = [&](int img) {
-    if constexpr (FIRST) {
-      const int v16 = per_c >> 4, total16 = cin * v16;       // 84-wide frames: 16-byte multiples
-#pragma unroll
-      for (int i = 0; i < NU; ++i) {
-        const int e = i * RB_CONV_THREADS + t;
-        pu[i] = make_uint4(0u, 0u, 0u, 0u);
-        if (e < total16) {
-          const int c = e / v16, q = e - c * v16;
-          const uint8_t* fp = rb_frame_ptr(a.src, img, c, cin, G::IP);
-          if (fp) pu[i] = *reinterpret_cast<const uint4*>(fp + iy0 * G::IH + q * 16);
-        }
-      }
-    } else if constexpr (VEC) {
-      const float* base = a.in_f + (int64_t)img * cin * G::IP;
-      const int v4 = per_c >> 2, total = cin * v4;
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        const int e = i * RB_CONV_THREADS + t;
-        const int ec = e < total ? e : total - 1;
-        const int c = ec / v4, q = ec - c * v4;
-        pv[i] = rb_ld4(base + c * G::IP + iy0 * G::IH + q * 4);
-      }
-    } else {
-      const float* base = a.in_f + (int64_t)img * cin * G::IP;
-      const int total = cin * per_c;
-#pragma unroll
-      for (int i = 0; i < NS; ++i) {
-        const int e = i * RB_CONV_THREADS + t;
-        const int ec = e < total ? e : total - 1;
-        const int c = ec / per_c, q = ec - c * per_c;
-        ps[i] = base[c * G::IP + iy0 * G::IH + q];
-      }
-    }
-  };
-  auto commit = [&]() {
-    if constexpr (FIRST) {
-      const int v16 = per_c >> 4, total16 = cin * v16;
-#pragma unroll
-      for (int i = 0; i < NU; ++i) {
-        const int e = i * RB_CONV_THREADS + t;
-        if (e < total16) {
-          const int c = e / v16, q = e - c * v16;
-          float* d = s_patch + c * PLANE + q * 16;
-          const unsigned wds[4] = {pu[i].x, pu[i].y, pu[i].z, pu[i].w};
-#pragma unroll
-          for (int wd = 0; wd < 4; ++wd)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) d[wd * 4 + b] = rb_unit((uint8_t)((wds[wd] >> (8 * b)) & 0xFFu));
-        }
-      }
-    } else if constexpr (VEC) {
-      const int v4 = per_c >> 2, total = cin * v4;
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        const int e = i * RB_CONV_THREADS + t;
-        if (e < total) {
-          const int c = e / v4, q = e - c * v4;
-          float* d = s_patch + c * PLANE + q * 4;
-          d[0] = pv[i].x; d[1] = pv[i].y; d[2] = pv[i].z; d[3] = pv[i].w;
-        }
-      }
-    } else {
-      const int total = cin * per_c;
-#pragma unroll
-      for (int i = 0; i < NS; ++i) {
-        const int e = i * RB_CONV_THREADS + t;
-        if (e < total) { const int c = e / per_c, q = e - c * per_c; s_patch[c * PLANE + q] = ps[i]; }
-      }
-    }
-  };
-
-  constexpr int KW = KPAD / RB_CONV_WAVES, HW = KW / 2;
-  const int kb = wave * KW;
-  int noff[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    int p = p0 + nt * 32 + (lane & 31);
-    if (p > G::P - 1) p = G::P - 1;                  // clamped lanes are never stored
-    noff[nt] = (p / G::OH - oy0) * G::S * G::IH + (p % G::OH) * G::S;
-  }
-  const int kh = lane >> 5, ml = lane & 31;
-  constexpr int EIT = (16 * 64) / RB_CONV_THREADS;
-  float bias_r[EIT];
-  int kos[HW];
-
-  issue(img0);
-  for (int img = img0; img < img_end; ++img) {
-    if (img == img0 || img == a.n_on) {               // block-uniform (every wave is past the previous image's MFMA loop)
-      const int net = img < a.n_on ? 0 : 1;
-      rb_stage_weights_t(s_w, a.w[net], cout0, a.cout - cout0 < 32 ? a.cout - cout0 : 32, K, KPAD);
-#pragma unroll
-      for (int it = 0; it < EIT; ++it) {
-        const int idx = t + it * RB_CONV_THREADS;
-        const int m = cout0 + rb_mfma_row(idx >> 6, idx & 63);
-        bias_r[it] = a.bias[net][m < a.cout ? m : a.cout - 1];
-      }
-    }
-    commit();
-    __syncthreads();            // patch (and slab) complete; the previous image's last reduction has been consumed
-    RB_MSTAMP(img == img0 ? 49 : img == img0 + 1 ? 53 : 57);
-    if (img + 1 < img_end) issue(img + 1);
-    if (img == img0) {
-#pragma unroll
-      for (int j = 0; j < HW; ++j) kos[j] = s_koff[kb + 2 * j + kh];
-    }
-    rb_f32x16 acc[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[nt][r] = 0.0f;
-#pragma unroll
-    for (int j = 0; j < HW; ++j) {
-      const float av = s_w[(kb + 2 * j + kh) * 33 + ml];
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) acc[nt] = rb_mfma32(av, s_patch[noff[nt] + kos[j]], acc[nt]);
-    }
-    RB_MSTAMP(img == img0 ? 50 : img == img0 + 1 ? 54 : 58);
-    // cross-wave sum one 32-position tile at a time, fixed order w0..w7 (as the one-image kernel)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      if (nt > 0) __syncthreads();                    // the previous tile's sums are no longer read
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s_red[(wave * 16 + r) * 64 + lane] = acc[nt][r];
-      __syncthreads();                                // (nt == NT - 1: every wave is also done with this image's patch)
-#pragma unroll
-      for (int it = 0; it < EIT; ++it) {
-        const int idx = t + it * RB_CONV_THREADS;
-        const int l = idx & 63, r = idx >> 6;
-        float v = s_red[(0 * 16 + r) * 64 + l];
-#pragma unroll
-        for (int wv = 1; wv < RB_CONV_WAVES; ++wv) v += s_red[(wv * 16 + r) * 64 + l];
-        const int m = cout0 + rb_mfma_row(r, l);
-        const int p = p0 + nt * 32 + (l & 31);
-        if (m < a.cout && p < G::P && p < p0 + PCH) {
-          const float o = fmaxf(v + bias_r[it], 0.0f);
-          a.out[((int64_t)img * a.cout + m) * G::P + p] = o;
-          if (a.out_blocked) {
-            const int k = m * G::P + p;                                   // x.view(-1, conv_output_size), model.py:71
-            a.out_blocked[((int64_t)(k >> 4) * a.rows_total + img) * 16 + (k & 15)] = o;
-          }
-        }
-      }
-      if (nt == 0) RB_MSTAMP(img == img0 ? 51 : img == img0 + 1 ? 55 : 59);
-    }
-    RB_MSTAMP(img == img0 ? 52 : img == img0 + 1 ? 56 : 60);
-  }
-  RB_MSTAMP(61);
-}
-
-// ---- large batches, later layers, WHOLE-K tiles: k_conv_fwd_multi's image loop around the t16 body ------------------------------
-// k_conv_fwd_multi above splits the reduction over its 8 waves and sums the partial tiles through LDS — per image NT rounds of
-// (16 stores, barrier, 8-way sum, barrier) during which the MFMA pipe idles: MFMA-busy 0.53-0.57 at batch 256 (profiles/
-// round5_sq_counters_*).  Here the workgroup is the t16 body's (rb_conv_fwd_body<..., T16 = 1>): one wave per 16-position x 16-channel
-// tile over the WHOLE reduction, the epilogue straight from the accumulators — no partial sums, no reduction scratch, two barriers per
-// image (patch complete / patch free).  The row-major 32-channel slab (and the bias terms) are set up once per net, the next image's
-// patch is in flight (registers) under this image's MFMA loop.  Same LDS image as the one-image t16 kernel (117 / 95 KB for the
-// canonical layers 2 / 3).  Needs cin * KK == KMAX, cin % 4 == 0, KMAX % 16 == 0, cout % 32 == 0 (host-checked).
+// ---- large batches, later layers: one weight slab per workgroup, a loop over images around the t16 body -------------------------
+// At 768 images the one-image workgroup above stages 34-76 KB of weights for 2.6-5.3 us of MFMAs, 6-15 times per CU.  Here a
+// workgroup owns (position chunk, 32-channel slab) and walks a.ipb images.  The workgroup is the t16 body's
+// (rb_conv_fwd_body<..., T16 = 1>): one wave per 16-position x 16-channel tile over the WHOLE reduction, the epilogue straight from
+// the accumulators — no partial sums, no reduction scratch (a split reduction idles the MFMA pipe during its per-image sums:
+// MFMA-busy 0.53-0.57 at batch 256, profiles/round5_sq_counters_*), two barriers per image (patch complete / patch free).  The
+// row-major 32-channel slab (and the bias terms) are set up once per net (again where the image range crosses from the online to
+// the target net), the next image's patch is in flight (registers) under this image's MFMA loop.  Same LDS image as the one-image
+// t16 kernel (117 / 95 KB for the canonical layers 2 / 3).  Needs cin * KK == KMAX, cin % 4 == 0, KMAX % 16 == 0, cout % 32 == 0
+// (true of every later layer of the canonical stack).
 // grid = (position chunks, cout / 32, image groups) or image-group-fastest (a.img_fast); block = 64 * NWV.
 template <class G, int NT, int PR, int KMAX, int PCH = 32 * NT>
 __global__ __launch_bounds__((64 * ConvFwdWaves<G, NT, PR, KMAX, false, PCH, false, 1>::NWV))
@@ -1146,11 +924,7 @@ struct ConvFwdFullLds {
   // 12 * 32 + 16).  As a 13th 32x32 tile it gave ONE SIMD four tiles and the others three (waves w and w + 4 share a SIMD).  It
   // runs instead as four 16x16x4 units — (channel half, reduction half), one on each of waves 4..7, i.e. one per SIMD — whose
   // two reduction halves meet through 4 KB of LDS behind the end-of-image barrier: 3.25 tiles per SIMD instead of 4 / 3 / 3 / 3.
-#if defined(RB_NO_TAIL16)      // (variant build for A/B runs)
-  static constexpr bool TAIL16 = false;
-#else
   static constexpr bool TAIL16 = (G::P % 32) != 0 && (G::P % 32) <= 16 && NTILES == 13 && RB_CONV_WAVES == 8 && (G::KS % 4) == 0 && (CMAX % 2) == 0;
-#endif
   static constexpr int TAILF = TAIL16 ? 4 * 4 * 64 : 0;
   static constexpr int FLOATS = KPAD * 33 + CMAX * G::IP + TAILF;
   static constexpr bool FITS = FLOATS * 4 <= 160 * 1024 && NTILES <= 2 * RB_CONV_WAVES && (G::IP % 16) == 0;
@@ -1407,9 +1181,9 @@ struct ConvLdsDxArgs {
   int img_fast;          // grid = (image groups, channel tiles, phase x position groups): see k_conv_fwd_lds
 };
 
-// MULTI (batches of 64 and more): a workgroup keeps its weight slab and walks a.ipb images — per image only the dY tile
-// is staged (31 KB against 76 KB of transposed weights for the third layer); the reduction scratch then has a region of
-// its own instead of overlaying the operands.
+// MULTI (batches of 64 and more, the data-efficient second layer; the canonical layers' image loop is k_conv_dx_t16_multi below):
+// a workgroup keeps its weight slab and walks a.ipb images — per image only the dY tile is staged; the reduction scratch then
+// has a region of its own instead of overlaying the operands.
 template <class G, int NT, int COUT, bool LAZY = false, bool MULTI = false>
 __global__ __launch_bounds__(RB_CONV_THREADS) void k_conv_dx_lds(ConvLdsDxArgs a) {
   constexpr int TMAX = (G::KS + G::S - 1) / G::S;           // taps per dimension of a phase

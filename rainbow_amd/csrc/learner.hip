@@ -140,6 +140,51 @@ static NetPtrs net_ptrs(const Layout& L, const float* params, const float* noise
   return p;
 }
 
+// ---------------------------------------------------------------------- RB_OPTS --
+// RB_OPTS="key=value,key=value" is the library's ONE tuning / test-hook variable, read when a learner handle is created, never
+// per launch.  Every key is a row of this table (DESIGN.md §8 repeats it); rb_learner_create refuses a key that is not, and an
+// entry without '=' or without an integer value.
+struct RbOpts {
+  int generic, fc_gemm, implicit_small, xs, act_fused, spec_draw, spec_stall, img_fast, conv_multi, conv_full, t16, dx_ipb, dw_ipb0, dw_ipb1, dw_ipb2;
+};
+static const struct { const char* key; int RbOpts::*field; int dflt; const char* what; } rb_opt_table[] = {
+  {"generic", &RbOpts::generic, 0, "1: every contraction on the gemm_core.h fallback; 2: the noisy-linear layers only"},
+  {"fc_gemm", &RbOpts::fc_gemm, -1, "hidden layer on the LDS-tiled GEMMs of fc_gemm.h: -1 = by shape (from 128 rows per net on), 1 = always, 0 = never"},
+  {"implicit_small", &RbOpts::implicit_small, 0, "test hook: RB_LEARNER_IMPLICIT_SIGMA on hidden layers of any size"},
+  {"xs", &RbOpts::xs, 0, "row splits of the hidden layer's input gradient: 0 = derived from the hidden size (ceil(2H / 256), at most 4)"},
+  {"act_fused", &RbOpts::act_fused, 1, "Agent.act as ONE launch (0: the per-layer launches)"},
+  {"spec_draw", &RbOpts::spec_draw, 0, "the early draw (opt-in: only append-free loops ever arm it)"},
+  {"spec_stall", &RbOpts::spec_stall, 0, "test hook: the early draw's go flag is never stored, the gate in front of the pair expires"},
+  {"img_fast", &RbOpts::img_fast, 1, "image-fastest block order of the conv launches (0: the order that image counts off a multiple of 8 get)"},
+  {"conv_multi", &RbOpts::conv_multi, -1, "images per workgroup of the conv forward: -1 = by shape (from 256 images on), 0 = one"},
+  {"conv_full", &RbOpts::conv_full, 1, "the first layer's whole-image kernel at large batches (0: the chunked kernel)"},
+  {"t16", &RbOpts::t16, 1, "the canonical first layer's u8 forward on whole-K 16x16x4 tiles (0: the split-K kernel that history < 4 gets)"},
+  {"dx_ipb", &RbOpts::dx_ipb, 0, "images per workgroup of the conv input gradients: 0 = by shape (from batch 64 on)"},
+  {"dw_ipb0", &RbOpts::dw_ipb0, 0, "images per workgroup of conv layer 0 in the weight-gradient launch: 0 = by shape"},
+  {"dw_ipb1", &RbOpts::dw_ipb1, 0, "... of conv layer 1"},
+  {"dw_ipb2", &RbOpts::dw_ipb2, 0, "... of conv layer 2"},
+};
+static int rb_opts_parse(const char* s, RbOpts* o) {
+  for (const auto& row : rb_opt_table) o->*row.field = row.dflt;
+  while (s && *s) {
+    const char* e = strchr(s, ',');
+    const size_t n = e ? (size_t)(e - s) : strlen(s);
+    const char* eq = (const char*)memchr(s, '=', n);
+    RB_REQUIRE(eq != nullptr && eq > s, "RB_OPTS: entry '%.*s' is not key=value", (int)n, s);
+    const size_t kl = (size_t)(eq - s);
+    int RbOpts::*field = nullptr;
+    for (const auto& row : rb_opt_table)
+      if (strlen(row.key) == kl && strncmp(row.key, s, kl) == 0) field = row.field;
+    RB_REQUIRE(field != nullptr, "RB_OPTS: unknown key '%.*s'", (int)kl, s);
+    char* end = nullptr;
+    const long v = strtol(eq + 1, &end, 10);
+    RB_REQUIRE(end == s + n && end > eq + 1, "RB_OPTS: key '%.*s' needs an integer value", (int)kl, s);
+    o->*field = (int)v;
+    s = e ? e + 1 : s + n;
+  }
+  return RB_OK;
+}
+
 // ---------------------------------------------------------------------- handle --
 struct rb_learner {
   rb_learner_config_t cfg;
@@ -161,19 +206,7 @@ struct rb_learner {
   float* dfeat_part;    // [xs][B][F]
   int lazy_dfeat;       // this step: the last conv layer's backward kernels sum the partials themselves (no k_dfeat_finish)
   int lazy_splits;
-  // test hooks read ONCE, when the handle is created (RB_OPTS, rb_opts below): they force the large-batch code paths and the
-  // fallback block order onto small fixtures — conv_multi (-1 = by image count), conv_full, dx_ipb (0 = by batch), img_fast
-  int opt_conv_multi, opt_conv_multi_t16, opt_conv_full, opt_dx_ipb, opt_dx_t16, opt_img_fast, opt_finish_tiled, opt_dw_ipb[3], opt_dw_balance, opt_wt_blocks;
-  int opt_h_dw_deep;    // ... and its weight gradient with all four column tiles' operands in flight (rb_nl_dw_body_pipe_all)
-  int opt_z_deep;       // the output layer's input gradient at batch > 32 with 8 row-steps of loads in flight (rb_nl_dx_body<4, 8>)
-  int opt_wb_auto;      // the priority write-back inside the hidden layer's backward launch through rb_update_auto (sorted batch: one wave)
-  int opt_h_deep;       // the hidden layer's input gradient at batch <= 32 with 8 row-steps of loads in flight (rb_nl_dx_body<2, 8>)
-  int opt_z_ct, opt_h_ct;   // column tiles per wave of the pipelined weight-gradient body (output / hidden layer)
-  int opt_z_narrow;     // ... on 32-column tiles (rb_nl_dx_body_tall<2>)
-  int opt_z_tall;       // the output layer's input gradient with 16 waves per workgroup (noisy_linear.h rb_nl_dx_body_tall)
-  int opt_t16;          // bit l: conv layer l's forward on the whole-K 16x16x4 kernel (conv_lds.h k_conv_fwd_t16) at small batches
-  int opt_implicit_small;
-  int opt_fc_gemm;      // hidden layer on the LDS-tiled GEMMs of fc_gemm.h: -1 = from 128 rows per net on (default), 1 = always, 0 = never
+  RbOpts opt;           // RB_OPTS, read ONCE when the handle is created (rb_opt_table above)
   float* gemm_part;     // split-K partial tiles of k_fc_gemm_fwd: one 64 KB tile per workgroup slot (n_cu of them)
   unsigned* gemm_ctr;   // its per-tile arrival counters (self-resetting)
   float* dw_part[3];    // [ws_l][cout][K+1]
@@ -193,7 +226,6 @@ struct rb_learner {
   unsigned* act_ctr;    // arrival counters of the one-launch act path (act_path.h k_act_fused; monotonic, sharded) + its error word
   unsigned act_epoch;   // launches of k_act_fused so far
   int n_cu;             // compute units of the device (the one-launch act path runs one workgroup per CU)
-  int opt_act_fused;    // RB_OPTS act_fused (default 1): Agent.act as ONE launch
   int rows_cap;         // image rows the forward buffers (act, hpart, h, feat_b, h_b, logits) hold: 3B, grown by act_batch
   int hs, xs, ws[3];    // split counts
   int dw_slices[3];     // slices actually written by the last conv weight-grad launch of each layer
@@ -230,12 +262,11 @@ struct rb_learner {
   // launch and runs — together with the NEXT call's draw — on the replay's own stream as soon as the head kernel is done; the next
   // call's sampler launch accepts the draw and carries only the noise and the pending optimiser pass.  Only an append-free,
   // constant-beta loop ever arms it (a PER benchmark; never main.py's loop), every wait is bounded at ~2 ms and fails safe, and the
-  // first expiry disables it on the handle.  opt_spec_stall (RB_OPTS spec_stall=1, test hook): the launch behind the head kernel does
+  // first expiry disables it on the handle.  RB_OPTS spec_stall=1 (test hook): the launch behind the head kernel does
   // not store the go flag — the gate in front of the pair expires.
   // (A SPLIT optimiser pass — the (mu, sigma) pair workgroups on a second stream beside the sampler and the conv forward, the hidden
   // layer's forward waiting in-kernel for their arrival — was built in round 5, bit-identical, and measured 177 us per step against
   // 161.5: profiles/round5_split_experiments.txt; removed, the code is commit 645f60a.)
-  int opt_spec_draw, opt_spec_stall;
   unsigned* go_flag;          // device word: epoch of the last head kernel known complete (stored by the launch behind it)
   unsigned go_epoch;
   int spec_now;               // this train_step: the write-back and the next draw go to the replay's stream
@@ -253,9 +284,6 @@ struct rb_learner {
   float delta_z;        // float32((Vmax - Vmin)/(Z-1))   agent.py:19,82
 };
 
-#ifndef RB_SPEC_DRAW_DEFAULT
-#define RB_SPEC_DRAW_DEFAULT 0    // RB_OPTS spec_draw: see rb_learner::opt_spec_draw (opt-in: only append-free loops ever arm it)
-#endif
 static int flush_update(rb_learner* l, hipStream_t stream);
 #define RB_FLUSH_UPDATE(l, stream)                                  \
   do {                                                              \
@@ -312,20 +340,6 @@ __global__ __launch_bounds__(256) void k_dfeat_finish(const float* part, int spl
       for (int u = 0; u < 8; ++u) acc += (s0 + u < splits) ? v[u] : 0.0f;
     }
     dfeat[i] = fv > 0.0f ? acc : 0.0f;
-  }
-}
-
-// conv weight/bias grads: sum the split-K slices in a fixed order (deterministic)
-__global__ __launch_bounds__(256) void k_reduce_conv_dw(const float* part, int splits, int cout, int K, float* gw,
-                                                         float* gb) {
-  const int64_t total = (int64_t)cout * (K + 1);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    float acc = 0.0f;
-#pragma unroll 8
-    for (int s = 0; s < splits; ++s) acc += part[(int64_t)s * total + i];   // independent loads, fixed add order
-    const int co = (int)(i / (K + 1)), col = (int)(i % (K + 1));
-    if (col < K) gw[(int64_t)co * K + col] = acc;
-    else gb[co] = acc;
   }
 }
 
@@ -599,11 +613,7 @@ __global__ __launch_bounds__(RB_HEAD_THREADS) void k_head(int B, int Z, int A, c
   // bin, 2 x 51 steps = 7 us for a TERMINAL transition, whose atoms all land in one bin — and with 256 samples per batch there is
   // almost always one: the launch was 12 us for 5.4 us workgroups (profiles/round6_wg_timeline_b256.txt).  For Z <= 64 the run lengths
   // come from one ballot of the run starts, and an owner fetches its run eight atoms per round trip, then adds them in order.
-#if defined(RB_HEAD_NO_SCAN)      // (variant build for A/B runs)
-  const bool by_ballot = false;
-#else
   const bool by_ballot = Z <= 64;
-#endif
   auto scatter_runs = [&](const int* s_key, const float* s_x, bool second) {      // wave 0, lane = atom
     const bool valid = lane < Z;
     const int key = s_key[valid ? lane : Z - 1];
@@ -871,9 +881,7 @@ __device__ __forceinline__ void rb_fused_dw_adam_tile(const ClipAdamArgs& a, con
     }
   }
 }
-#ifndef RB_ADAM_MINWAVES
 #define RB_ADAM_MINWAVES 1
-#endif
 template <int RB_ADAM_UNROLL, bool WT, bool FUSED>   // float4 quadruples (p, g, m, v) in flight per thread; WT: write-through stores
 __global__ __launch_bounds__(256, RB_ADAM_MINWAVES) void k_clip_adam(ClipAdamArgs a, FusedDwAdamArgs f) {
   __shared__ float s_red[18];      // [0, 16) rb_block_sum's wave slots; [16], [17] the bias-correction scalars (slots of their own:
@@ -995,18 +1003,20 @@ static int launch_conv_fwd_lds(rb_learner* l, int layer, int n_on, int n_tg, con
   a.ipb = 1;
   a.img_fast = 0;
   static const char* const tags[3] = {"conv1_fwd:k_conv_fwd_lds", "conv2_fwd:k_conv_fwd_lds", "conv3_fwd:k_conv_fwd_lds"};
+  // whole-K 16x16x4 tiles, one wave per tile, no cross-wave reduction (conv_lds.h T16).  Every later layer of the canonical stack
+  // qualifies (cin * KK == KMAX and cout % 32 == 0 by construction); the data-efficient ones do not (K % 16 != 0, 9 positions)
+  constexpr bool T16_OK = KMAX % 16 == 0 && (KMAX / G::KK) % 4 == 0 && 2 * ((PCH + 15) / 16) <= 16 && (PCH % 16 == 0 || PCH >= G::P) && G::P > 16;
   // large batches: one round of workgroups, each keeping its weight slab for ipb images of one net (conv_lds.h)
-  const bool multi_forced = l->opt_conv_multi >= 0;                      // RB_CONV_MULTI: images per workgroup (0 = off)
+  const bool multi_forced = l->opt.conv_multi >= 0;
   int ipb = 0;
-  if (multi_forced) ipb = l->opt_conv_multi;
+  if (multi_forced) ipb = l->opt.conv_multi;
   else if (n_on + n_tg >= 256) {
     const int per_img = (int)(rb_div_up(G::P, PCH) * rb_div_up(c.cout, 32));
     ipb = (int)rb_div_up((int64_t)(n_on + n_tg) * per_img, 256);
   }
   if constexpr (FIRST && ConvFwdFullLds<G, KMAX>::FITS) {
-    // first layer: whole image per workgroup, whole reduction per wave (RB_CONV_FULL=0: the chunked kernel below)
-    const bool full_off = !l->opt_conv_full;
-    if (ipb > 0 && !src.f32 && c.cout <= 32 && !a.out_blocked && !full_off && c.cin * G::KK == KMAX && (KMAX & 1) == 0) {
+    // first layer: whole image per workgroup, whole reduction per wave
+    if (ipb > 0 && !src.f32 && c.cout <= 32 && !a.out_blocked && l->opt.conv_full && c.cin * G::KK == KMAX && (KMAX & 1) == 0) {
       int fi = ipb;
       if (!multi_forced) fi = (int)rb_div_up(n_on + n_tg, 256);         // one round of workgroups
       a.ipb = fi;
@@ -1016,37 +1026,29 @@ static int launch_conv_fwd_lds(rb_learner* l, int layer, int n_on, int n_tg, con
       return RB_OK;
     }
   }
-  if constexpr (!FIRST && ConvFwdMultiLds<G, PR, KMAX>::FITS) {      // (first layers: k_conv_fwd_full above)
+  if constexpr (!FIRST && T16_OK) {      // (first layers: k_conv_fwd_full above)
     if (ipb > 0) {
       a.ipb = ipb;
       const unsigned ngroups = (unsigned)rb_div_up(n_on + n_tg, ipb);
       dim3 gridm((unsigned)rb_div_up(G::P, PCH), (unsigned)rb_div_up(c.cout, 32), ngroups);
-      if (l->opt_img_fast && ngroups % 8 == 0) {     // image-group-fastest block order (layers 2 and 3 use the same ipb)
+      if (l->opt.img_fast && ngroups % 8 == 0) {     // image-group-fastest block order (layers 2 and 3 use the same ipb)
         a.img_fast = 1;
         gridm = dim3(ngroups, (unsigned)rb_div_up(c.cout, 32), (unsigned)rb_div_up(G::P, PCH));
       }
-      if constexpr (KMAX % 16 == 0 && (KMAX / G::KK) % 4 == 0 && 2 * ((PCH + 15) / 16) <= 16 && (PCH % 16 == 0 || PCH >= G::P) && G::P > 16) {
-        // whole-K 16x16x4 tiles in the image loop as well (conv_lds.h k_conv_fwd_multi_t16; RB_OPTS conv_multi_t16=0: the split-K body)
-        if (l->opt_conv_multi_t16 && ((l->opt_t16 >> layer) & 1) && c.cin * G::KK == KMAX && c.cout % 32 == 0) {
-          constexpr int NWV = ConvFwdWaves<G, NT, PR, KMAX, false, PCH, false, 1>::NWV;
-          RB_LAUNCH_T(tags[layer], (k_conv_fwd_multi_t16<G, NT, PR, KMAX, PCH>), gridm, dim3(64 * NWV), stream, a);
-          RB_LAUNCH_CHECK();
-          return RB_OK;
-        }
-      }
-      RB_LAUNCH_T(tags[layer], (k_conv_fwd_multi<G, NT, PR, KMAX, FIRST, PCH>), gridm, dim3(RB_CONV_THREADS), stream, a);
+      constexpr int NWV = ConvFwdWaves<G, NT, PR, KMAX, false, PCH, false, 1>::NWV;
+      RB_LAUNCH_T(tags[layer], (k_conv_fwd_multi_t16<G, NT, PR, KMAX, PCH>), gridm, dim3(64 * NWV), stream, a);
       RB_LAUNCH_CHECK();
       return RB_OK;
     }
   }
   dim3 grid1((unsigned)rb_div_up(G::P, PCH), (unsigned)rb_div_up(c.cout, 32), (unsigned)(n_on + n_tg));
-  if (l->opt_img_fast && (n_on + n_tg) % 8 == 0) {     // RB_CONV_IMGFAST: image-fastest block order (XCD = image mod 8 in every layer)
+  if (l->opt.img_fast && (n_on + n_tg) % 8 == 0) {     // image-fastest block order (XCD = image mod 8 in every layer)
     a.img_fast = 1;
     grid1 = dim3((unsigned)(n_on + n_tg), (unsigned)rb_div_up(c.cout, 32), (unsigned)rb_div_up(G::P, PCH));
   }
-  if constexpr (KMAX % 16 == 0 && (KMAX / G::KK) % 4 == 0 && 2 * ((PCH + 15) / 16) <= 16 && (PCH % 16 == 0 || PCH >= G::P) && G::P > 16) {
-    // whole-K 16x16x4 tiles, one wave per tile, no cross-wave reduction (conv_lds.h T16): the learn step's u8 / f32 inputs
-    if (((l->opt_t16 >> layer) & 1) && !(FIRST && src.f32) && c.cin * G::KK == KMAX && c.cout % 32 == 0) {
+  if constexpr (T16_OK) {
+    // the first layer: u8 frames of a full history only (f32 states — act / evaluate — and history < 4 run the split-K kernel below)
+    if (!FIRST || (l->opt.t16 && !src.f32 && c.cin * G::KK == KMAX)) {
       constexpr int CTW = 1;                    // channel tiles per wave (2 measured slower for the first layer: 5-wave staging)
       constexpr int NWV = ConvFwdWaves<G, NT, PR, KMAX, FIRST, PCH, false, CTW>::NWV;
       RB_LAUNCH_T(tags[layer], (k_conv_fwd_t16<G, NT, PR, KMAX, FIRST, PCH, CTW>), grid1, dim3(64 * NWV), stream, a);
@@ -1054,12 +1056,15 @@ static int launch_conv_fwd_lds(rb_learner* l, int layer, int n_on, int n_tg, con
       return RB_OK;
     }
   }
-  if (FIRST && src.f32) {       // float states (act / evaluate): an instantiation of its own (conv_lds.h F32SRC)
-    RB_LAUNCH_T(tags[layer], (k_conv_fwd_lds<G, NT, PR, KMAX, FIRST, PCH, FIRST>), grid1, dim3(RB_CONV_THREADS), stream, a);
-  } else {
-    RB_LAUNCH_T(tags[layer], (k_conv_fwd_lds<G, NT, PR, KMAX, FIRST, PCH>), grid1, dim3(RB_CONV_THREADS), stream, a);
+  // split-K 32x32x2 tiles: first layers (above) and the data-efficient second layer
+  if constexpr (FIRST || !T16_OK) {
+    if (FIRST && src.f32) {       // float states (act / evaluate): an instantiation of its own (conv_lds.h F32SRC)
+      RB_LAUNCH_T(tags[layer], (k_conv_fwd_lds<G, NT, PR, KMAX, FIRST, PCH, FIRST>), grid1, dim3(RB_CONV_THREADS), stream, a);
+    } else {
+      RB_LAUNCH_T(tags[layer], (k_conv_fwd_lds<G, NT, PR, KMAX, FIRST, PCH>), grid1, dim3(RB_CONV_THREADS), stream, a);
+    }
+    RB_LAUNCH_CHECK();
   }
-  RB_LAUNCH_CHECK();
   return RB_OK;
 }
 
@@ -1130,7 +1135,7 @@ static int forward(rb_learner* l, int n_on, int n_tg, const ImgSrc& src, const N
     // (16-row m-chunks — 384 workgroups, every CU busy — measured 20.8 us against 16.2: the tiles are re-read four times)
     const dim3 hg((unsigned)(2 * ht16), 1, 2 * mch32), hb(64 * RB_NL_FWD_WAVES);
     // from 128 rows per net on the layer is a GEMM, not a weight stream: 128 x 128 LDS tiles, split-K over the idle CUs (fc_gemm.h)
-    const bool gemm = l->gemm_part && (l->opt_fc_gemm == 1 || (l->opt_fc_gemm < 0 && m_max >= 128));
+    const bool gemm = l->gemm_part && (l->opt.fc_gemm == 1 || (l->opt.fc_gemm < 0 && m_max >= 128));
     if (gemm) {
       FcGemmFwdArgs ga;
       ga.f = a;
@@ -1190,14 +1195,14 @@ static int forward(rb_learner* l, int n_on, int n_tg, const ImgSrc& src, const N
 
 // The data gradient of conv layer `layer` (>= 1) on the whole-K 16x16x4 tile kernel (conv_lds.h k_conv_dx_t16_multi): the image-loop
 // form, i.e. batches of 64 and more (or RB_OPTS dx_ipb > 1, the test hook), the canonical later layers' geometries (64 output
-// channels, kernel size a multiple of the stride).  RB_OPTS dx_t16=0: k_conv_dx_lds<..., MULTI>.  Decides the layout of conv_wT too.
+// channels, kernel size a multiple of the stride); the data-efficient second layer's image loop is k_conv_dx_lds<..., MULTI>.
+// Decides the layout of conv_wT too.
+static constexpr bool dx_t16_geom(int ks, int s, int ih) { return (ks == 4 && s == 2 && ih == 20) || (ks == 3 && s == 1 && ih == 9); }   // GeomC2 / GeomC3
 static bool dx_uses_t16(const rb_learner* l, int layer) {
   const Layout& L = l->L;
-  if (layer < 1 || layer >= L.nconv || !l->fast_conv || !l->conv_wT[layer] || !l->opt_dx_t16) return false;
+  if (layer < 1 || layer >= L.nconv || !l->fast_conv || !l->conv_wT[layer]) return false;
   const ConvLayer& c = L.conv[layer];
-  if (c.cout != 64 || c.cin % 32 != 0 || c.ks % c.s != 0) return false;
-  if (!((c.ks == 4 && c.s == 2 && c.ih == 20) || (c.ks == 3 && c.s == 1 && c.ih == 9))) return false;      // GeomC2 / GeomC3 (ConvDxT16<G, 64>::OK)
-  return L.B >= 64 || l->opt_dx_ipb > 1;
+  return dx_t16_geom(c.ks, c.s, c.ih) && (L.B >= 64 || l->opt.dx_ipb > 1);
 }
 
 // mode bit 0: weight/bias grads (+ split reduction); bit 1: data grads into dact[layer-1]
@@ -1206,8 +1211,6 @@ static int launch_conv_bwd(rb_learner* l, int layer, const uint8_t* states, hipS
   const Layout& L = l->L;
   const ConvLayer& c = L.conv[layer];
   const int K = c.K();
-  float* gw = l->grads + L.conv_w[layer];
-  float* gb = l->grads + L.conv_b[layer];
   const int splits = l->ws[layer];
   if (!(mode & 1)) {
   } else if (layer == 0) {
@@ -1226,7 +1229,6 @@ static int launch_conv_bwd(rb_learner* l, int layer, const uint8_t* states, hipS
   if (mode & 1) {
     RB_LAUNCH_CHECK();
     l->dw_slices[layer] = splits;   // summed by k_reduce_conv_dw_all after the last layer
-    (void)gw; (void)gb;
   }
   if (!(mode & 2)) return RB_OK;
   if constexpr (G::IH == 84) {
@@ -1247,7 +1249,7 @@ static int launch_conv_bwd(rb_learner* l, int layer, const uint8_t* states, hipS
     const unsigned groups = (unsigned)rb_div_up(NT_ALL, NT);
     static const char* const tags[3] = {"conv1_dx:k_conv_dx_lds", "conv2_dx:k_conv_dx_lds", "conv3_dx:k_conv_dx_lds"};
     // batches of 64 and more: about one round of workgroups over the chip, each keeping its weight slab for ipb images
-    const int ipb_env = l->opt_dx_ipb;                                            // RB_DX_IPB (1 = one image each)
+    const int ipb_env = l->opt.dx_ipb;                                            // (1 = one image each)
     const int per_img = (G::S * G::S) * (int)groups * (int)rb_div_up(c.cin, 32);
     int ipb = 1;
     if (ipb_env > 0) ipb = ipb_env;
@@ -1255,35 +1257,35 @@ static int launch_conv_bwd(rb_learner* l, int layer, const uint8_t* states, hipS
       while (per_img * (int)rb_div_up(L.B, ipb) > 256) ++ipb;
       // image-group-fastest order wants a group count that is a multiple of 8 — and the same groups as the next layer's launch and
       // the weight-gradient launch (8 images each at batch 256), so that a group's dY stays in one XCD's L2 down the chain
-      if (l->opt_img_fast)
+      if (l->opt.img_fast)
         while (ipb < L.B && (rb_div_up(L.B, ipb) % 8 != 0 || L.B % ipb != 0)) ++ipb;
     }
     a.ipb = ipb; a.batch = L.B;
     dim3 grid((unsigned)(G::S * G::S) * groups, (unsigned)rb_div_up(c.cin, 32), (unsigned)rb_div_up(L.B, ipb));
     a.img_fast = 0;
-    if (l->opt_img_fast && L.B % ipb == 0 && (L.B / ipb) % 8 == 0) {      // image(-group)-fastest block order: image i on XCD i mod 8 in every conv launch
+    if (l->opt.img_fast && L.B % ipb == 0 && (L.B / ipb) % 8 == 0) {      // image(-group)-fastest block order: image i on XCD i mod 8 in every conv launch
       a.img_fast = 1;
       grid = dim3((unsigned)(L.B / ipb), (unsigned)rb_div_up(c.cin, 32), (unsigned)(G::S * G::S) * groups);
     }
-    if constexpr (ConvDxT16<G, 64>::OK) {
+    if constexpr (dx_t16_geom(G::KS, G::S, G::IH)) {
       if (dx_uses_t16(l, layer)) {
         // whole-K tiles: a workgroup per (phase, 32 input channels, image group), about one round of 256
         const int units = G::S * G::S * (int)rb_div_up(c.cin, 32);
         int tp = ipb_env > 0 ? ipb_env : (int)rb_div_up((int64_t)units * L.B, 256);
         if (tp < 1) tp = 1;
-        if (ipb_env <= 0 && l->opt_img_fast)
+        if (ipb_env <= 0 && l->opt.img_fast)
           while (tp < L.B && (rb_div_up(L.B, tp) % 8 != 0 || L.B % tp != 0)) ++tp;
         a.ipb = tp;
         const unsigned ng = (unsigned)rb_div_up(L.B, tp);
-        a.img_fast = (l->opt_img_fast && L.B % tp == 0 && ng % 8 == 0) ? 1 : 0;
+        a.img_fast = (l->opt.img_fast && L.B % tp == 0 && ng % 8 == 0) ? 1 : 0;
         const dim3 gt = a.img_fast ? dim3(ng, (unsigned)rb_div_up(c.cin, 32), (unsigned)(G::S * G::S))
                                    : dim3((unsigned)(G::S * G::S), (unsigned)rb_div_up(c.cin, 32), ng);
         RB_LAUNCH_T(tags[layer], (k_conv_dx_t16_multi<G, 64, lazy>), gt, dim3(64 * ConvDxT16<G, 64>::NWV), stream, a);
         RB_LAUNCH_CHECK();
         return RB_OK;
       }
-    }
-    if (ipb > 1) { RB_LAUNCH_T(tags[layer], (k_conv_dx_lds<G, NT, 64, lazy, true>), grid, dim3(RB_CONV_THREADS), stream, a); }
+      RB_LAUNCH_T(tags[layer], (k_conv_dx_lds<G, NT, 64, lazy, false>), grid, dim3(RB_CONV_THREADS), stream, a);
+    } else if (ipb > 1) { RB_LAUNCH_T(tags[layer], (k_conv_dx_lds<G, NT, 64, lazy, true>), grid, dim3(RB_CONV_THREADS), stream, a); }
     else { RB_LAUNCH_T(tags[layer], (k_conv_dx_lds<G, NT, 64, lazy, false>), grid, dim3(RB_CONV_THREADS), stream, a); }
     RB_LAUNCH_CHECK();
   } else if (layer > 0) {
@@ -1318,7 +1320,7 @@ static int conv_dw_all(rb_learner* l, hipStream_t stream) {
   // and the layers' images cost differently (7.5 / 7.4 / 6.2 us per image at batch 256, tools/wg_timeline.py): with 8 images
   // everywhere the launch was 224 workgroups of 60 / 59 / 50 us on 256 CUs; 7 / 7 / 8 images are 249 workgroups of 52 / 52 / 50 us
   // (-7.6 us per step, profiles/round6_dw_layer_ipb_ab.txt).  Smallest longest workgroup that still fits ONE round over the CUs.
-  if (L.B > 32 && L.nconv == 3 && l->opt_dw_balance) {
+  if (L.B > 32 && L.nconv == 3) {
     const int cost[3] = {75, 74, 62};
     const int chunks0 = (L.conv[0].oh + 6) / 7, ct[3] = {(int)rb_div_up(L.conv[0].cout, 32), (int)rb_div_up(L.conv[1].cout, 32), (int)rb_div_up(L.conv[2].cout, 32)};
     int best_t = ipb_all * cost[0], best[3] = {ipb_all, ipb_all, ipb_all};
@@ -1334,8 +1336,9 @@ static int conv_dw_all(rb_learner* l, hipStream_t stream) {
         }
     for (int i = 0; i < 3; ++i) a.ipb[i] = best[i];
   }
+  const int dw_ipb[3] = {l->opt.dw_ipb0, l->opt.dw_ipb1, l->opt.dw_ipb2};
   for (int i = 0; i < L.nconv; ++i) {
-    if (l->opt_dw_ipb[i] > 0) a.ipb[i] = l->opt_dw_ipb[i];
+    if (dw_ipb[i] > 0) a.ipb[i] = dw_ipb[i];
     if (a.ipb[i] > L.B) a.ipb[i] = L.B;
     if (a.ipb[i] != ipb_all) uniform = false;
     const int groups = (int)rb_div_up(L.B, a.ipb[i]);
@@ -1357,7 +1360,7 @@ static int conv_dw_all(rb_learner* l, hipStream_t stream) {
   for (int i = L.nconv; i < 3; ++i) { a.nblocks[i] = 0; a.cotiles[i] = 1; a.layer[i] = a.layer[0]; }
   // image-fastest decode (an image group's workgroups of every layer on XCD group mod 8, where the input-gradient chain left
   // its dY): block ranges and the group count must be multiples of 8
-  a.img_fast = (l->opt_img_fast && uniform && (int)rb_div_up(L.B, ipb_all) % 8 == 0 && a.nblocks[0] % 8 == 0 && a.nblocks[1] % 8 == 0) ? 1 : 0;
+  a.img_fast = (l->opt.img_fast && uniform && (int)rb_div_up(L.B, ipb_all) % 8 == 0 && a.nblocks[0] % 8 == 0 && a.nblocks[1] % 8 == 0) ? 1 : 0;
   // (a pipelined body — two operand sets in LDS, the next image's loads in flight under this image's MFMAs — was built in round 5,
   // bit-identical, and measured SLOWER at batch 256: 75.9 against 64.5 us for this launch, profiles/round5_experiments.txt; removed)
   if (L.nconv == 3) {
@@ -1499,10 +1502,13 @@ int rb_learner_create(rb_learner_t** out, const rb_learner_config_t* cfg, float*
   Layout L;
   int rc = make_layout(cfg, &L);
   if (rc != RB_OK) return rc;
+  RbOpts opt;
+  rc = rb_opts_parse(getenv("RB_OPTS"), &opt);
+  if (rc != RB_OK) return rc;
   rb_learner* l = new (std::nothrow) rb_learner();
   if (!l) { rb_set_error("rb_learner_create: host OOM"); return RB_ERR_OOM; }
   memset(l, 0, sizeof(*l));
-  l->cfg = *cfg; l->L = L;
+  l->cfg = *cfg; l->L = L; l->opt = opt;
   l->p_online = online_params_dev; l->p_target = target_params_dev; l->grads = grads_dev;
   l->n_online = online_noise_dev; l->n_target = target_noise_dev;
   l->seed = seed; l->noise_epoch = 0;
@@ -1516,33 +1522,10 @@ int rb_learner_create(rb_learner_t** out, const rb_learner_config_t* cfg, float*
   l->gamma_n = (float)pow(cfg->discount, (double)cfg->multi_step);
   l->delta_z = (float)(((double)cfg->v_max - (double)cfg->v_min) / (double)(cfg->atoms - 1));
   const int B = L.B, NI = 3 * B;
-  // split-K factors: aim for >= ~2 workgroups per CU on the 256-CU part
-  // RB_OPTS (rb_common.h): generic=1 forces the gemm_core fallback for every contraction, generic=2 for the noisy-linear
-  // layers only (both exercised by the CPU tests); the rest are test hooks that force the large-batch paths onto small fixtures
-  const int generic = rb_opt("generic", 0);
+  const int generic = l->opt.generic;
   l->fast_fc = (L.F % 32 == 0 && L.H % 32 == 0 && L.F <= RB_FWD2_KMAX && L.H <= RB_FWD2_KMAX && generic == 0) ? 1 : 0;
   l->fast_conv = (L.hist <= 4 && generic != 1) ? 1 : 0;
-  l->opt_conv_multi = rb_opt("conv_multi", -1);       // images per workgroup of the conv forward (-1: by image count)
-  l->opt_conv_multi_t16 = rb_opt("conv_multi_t16", 1);    // the image loop on whole-K 16x16x4 tiles (0: the split-K body)
-  l->opt_dx_t16 = rb_opt("dx_t16", 1);                    // the image-loop conv data gradient on whole-K 16x16x4 tiles (0: the split-K body)
-  l->opt_finish_tiled = rb_opt("finish_tiled", 1);        // rb_learner_finish_grads: the hidden layer's replica-mean weight gradient on 128 x 128 tiles
-  l->opt_conv_full = rb_opt("conv_full", 1);          // first layer's whole-image kernel at large batches
-  l->opt_wt_blocks = rb_opt("wt_blocks", 48);          // tenant workgroups of the head launch per weight-operand job
-  l->opt_dw_balance = rb_opt("dw_balance", 1);         // 0: the same number of images per workgroup in every layer of the weight-gradient launch
-  l->opt_dw_ipb[0] = rb_opt("dw_ipb0", 0); l->opt_dw_ipb[1] = rb_opt("dw_ipb1", 0); l->opt_dw_ipb[2] = rb_opt("dw_ipb2", 0);
-  l->opt_dx_ipb = rb_opt("dx_ipb", 0);                // images per workgroup of the conv input gradients (0: by batch)
-  l->opt_img_fast = rb_opt("img_fast", 1);            // image-fastest block order of the conv launches (0: the fallback order)
-  l->opt_z_tall = rb_opt("z_tall", 1);
-  l->opt_z_narrow = rb_opt("z_narrow", 1);
-  l->opt_h_deep = rb_opt("h_deep", 1);
-  l->opt_wb_auto = rb_opt("wb_auto", 1);
-  l->opt_z_deep = rb_opt("z_deep", 1);
-  l->opt_h_dw_deep = rb_opt("h_dw_deep", 1);
-  l->opt_z_ct = rb_opt("z_ct", 2); if (l->opt_z_ct < 1) l->opt_z_ct = 1;
-  l->opt_h_ct = rb_opt("h_ct", 4); if (l->opt_h_ct < 1) l->opt_h_ct = 1;
-  l->opt_t16 = rb_opt("t16", 7);                      // conv forward layers on k_conv_fwd_t16 (bit per layer)
-  l->opt_implicit_small = rb_opt("implicit_small", 0);   // test hook: RB_LEARNER_IMPLICIT_SIGMA on hidden layers of any size
-  l->opt_fc_gemm = rb_opt("fc_gemm", -1);             // hidden layer as LDS-tiled GEMMs (fc_gemm.h): -1 = from 128 rows on
+  // split-K factors: aim for >= ~2 workgroups per CU on the 256-CU part
   if (l->fast_fc) {
     l->hs = pick_splits(2 * rb_div_up(L.H, 32) * 2 * rb_div_up(2 * B, 64), L.F / 16 / RB_NL_FWD_WAVES, 512);
     // input-gradient row splits: 256 weight rows per workgroup (64 per wave = 4 sixteen-row iterations); measured
@@ -1550,7 +1533,7 @@ int rb_learner_create(rb_learner_t** out, const rb_learner_config_t* cfg, float*
     // (at most 4: the consumers of the partials — the last conv layer's dX and dW kernels — sum up to 4 of them while staging)
     l->xs = (int)rb_div_up(2 * L.H, 256);
     if (l->xs > 4) l->xs = 4;
-    l->xs = rb_opt("xs", l->xs);
+    if (l->opt.xs > 0) l->xs = l->opt.xs;
   } else {
     l->hs = pick_splits(rb_div_up(2 * B, 64) * rb_div_up(2 * L.H, 64) * 2, (L.F + 15) / 16, 512);
     l->xs = pick_splits(rb_div_up(B, 32) * rb_div_up(L.F, 64), (2 * L.H + 15) / 16, 512);
@@ -1611,10 +1594,7 @@ int rb_learner_create(rb_learner_t** out, const rb_learner_config_t* cfg, float*
   RB_ALLOC(l->act_ctr, 6 * RB_FAN_SHARDS * RB_FAN_STRIDE + 32);
 #undef RB_ALLOC
   RB_HIP_TRY(hipMemset(l->act_ctr, 0, (6 * RB_FAN_SHARDS * RB_FAN_STRIDE + 32) * 4));
-  l->opt_act_fused = rb_opt("act_fused", 1);
-  l->opt_spec_draw = rb_opt("spec_draw", RB_SPEC_DRAW_DEFAULT);
-  l->opt_spec_stall = rb_opt("spec_stall", 0);
-  if (l->opt_spec_draw) {
+  if (l->opt.spec_draw) {
     hipError_t e = rb_dev_malloc((void**)&l->go_flag, 64);
     if (e != hipSuccess) { rb_set_error("rb_learner_create: hipMalloc failed: %s", hipGetErrorString(e)); rb_learner_destroy(l); return RB_ERR_OOM; }
     RB_HIP_TRY(hipMemset(l->go_flag, 0, 64));
@@ -1629,7 +1609,7 @@ int rb_learner_create(rb_learner_t** out, const rb_learner_config_t* cfg, float*
     l->n_cu = cus;
   }
 #endif
-  if (l->fast_fc && l->opt_fc_gemm != 0) {
+  if (l->fast_fc && l->opt.fc_gemm != 0) {
     // split-K scratch of k_fc_gemm_fwd: tiles * S <= n_cu whenever S > 1, one 128 x 128 partial tile each
     hipError_t e = rb_dev_malloc((void**)&l->gemm_part, (size_t)l->n_cu * RB_TG_T * RB_TG_T * 4);
     if (e == hipSuccess) e = rb_dev_malloc((void**)&l->gemm_ctr, 1024 * 4);
@@ -1712,7 +1692,7 @@ int rb_learner_reset_noise(rb_learner_t* l, int32_t which, const float* raw_norm
 static int act_forward_single(rb_learner* l, const float* state_dev, const NetPtrs& on, int noisy, hipStream_t stream,
                               int32_t* head_action_out, float* head_q_out) {
   const Layout& L = l->L;
-  if (!l->fast_fc || (L.F & 3) || (L.H & 3)) return RB_ERR_STATE;   // RB_GENERIC_GEMM_ONLY=1 also lands here
+  if (!l->fast_fc || (L.F & 3) || (L.H & 3)) return RB_ERR_STATE;   // RB_OPTS generic=1 / 2 also lands here
   int rg[3];
   for (int layer = 0; layer < L.nconv; ++layer) {   // output rows per workgroup: <= 128 positions, patch fits the LDS
     const ConvLayer& c = L.conv[layer];
@@ -1739,7 +1719,7 @@ static int act_forward_single(rb_learner* l, const float* state_dev, const NetPt
   ActFcArgs& z = f.z;
   z.x = l->h; z.w = nl_z(on); z.K = L.H; z.n_rows = L.NZ; z.split_row = L.Z; z.x_off1 = L.H; z.ein_off1 = L.H;
   z.out = l->logits; z.relu = 0; z.mu_only = noisy ? 0 : 1;
-  bool can_fuse = l->opt_act_fused != 0;
+  bool can_fuse = l->opt.act_fused != 0;
   // (a captured launch would replay a stale launch number: under stream capture the per-layer launches below run instead)
   if (can_fuse && rb_stream_capturing(stream)) can_fuse = false;
   if (can_fuse) {
@@ -1985,7 +1965,7 @@ static int learn_impl(rb_learner_t* l, const ImgSrc& src, const uint8_t* states_
                                      dx_uses_t16(l, layer) ? 1 : 0};
       }
       if (n_jobs == 1) tn.job[1] = tn.job[0];
-      tn.per_job = n_jobs > 0 ? l->opt_wt_blocks : 0;                  // (one element or two per thread: the tenants must stay shorter than the head)
+      tn.per_job = n_jobs > 0 ? 48 : 0;                  // workgroups per job (one element or two per thread: the tenants must stay shorter than the head)
     }
     const dim3 hgrid((unsigned)(B + (n_jobs > 0 ? 2 * tn.per_job : 0))), hblock((unsigned)(64 * hwaves));
 #define RB_HEAD_ARGS B, L.Z, L.A, (const float*)l->logits, actions_dev, returns_dev, nonterminals_dev, weights_dev, (const float*)l->support, \
@@ -2007,14 +1987,13 @@ static int learn_impl(rb_learner_t* l, const ImgSrc& src, const uint8_t* states_
   if (l->fast_fc) {
     // ---- output layer: weight/bias grads and (ReLU-masked) input grads in one launch
     // sum-of-squares slots (clip_grad_norm_ without re-reading the gradient): [fc_z dW waves | fc_h dW waves | conv reduce blocks]
-    // pipelined weight-gradient body (one reduction pass per tile, i.e. batch <= 32): column tiles per wave
+    // pipelined weight-gradient body (one reduction pass per tile, i.e. batch <= 32): 256-column tiles per wave and workgroup
     const bool pipe = B <= 32 && !exch;
-    const int z_ct = pipe ? l->opt_z_ct : 0, h_ct = pipe ? l->opt_h_ct : 0;     // (RB_OPTS z_ct / h_ct: 256-column tiles per wave and workgroup)
+    const int z_ct = pipe ? 2 : 0, h_ct = pipe ? 4 : 0;
     FcDwPlan zp = fc_dw_plan(l, on, 0, l->dlogits, l->h, B, z_ct);
     FcDwPlan hp = fc_dw_plan(l, on, 1, l->dh, feat, B, h_ct);
-    hp.a.deep = l->opt_h_dw_deep;
     // batch >= 128: the hidden layer's two gradients as LDS-tiled GEMMs in one launch (fc_gemm.h k_fc_gemm_bwd)
-    const bool gemm_bwd = !exch && l->gemm_part && (l->opt_fc_gemm == 1 || (l->opt_fc_gemm < 0 && B >= 128));
+    const bool gemm_bwd = !exch && l->gemm_part && (l->opt.fc_gemm == 1 || (l->opt.fc_gemm < 0 && B >= 128));
     const int g_nt = (int)rb_div_up(2 * L.H, RB_TG_T), g_kt = (int)rb_div_up(L.F, RB_TG_T);
     if (gemm_bwd) hp.slots = 8 * g_nt * g_kt;             // one sum-of-squares slot per wave of a weight-gradient tile
     int64_t conv_out = 0;
@@ -2031,7 +2010,7 @@ static int learn_impl(rb_learner_t* l, const ImgSrc& src, const uint8_t* states_
     // adjacent mu | sigma arrays
     const bool implicit_sigma = (l->flags & RB_LEARNER_IMPLICIT_SIGMA) && ((pipe && h_ct > 0) || gemm_bwd) && fuse_norm && !defer_dw &&
                                 L.h_sigma == L.h_mu + (int64_t)2 * L.H * L.F && (L.F % 4) == 0 && (L.h_mu % 4) == 0 &&
-                                ((int64_t)2 * L.H * L.F >= ((int64_t)1 << 20) || l->opt_implicit_small);   // (the data-efficient
+                                ((int64_t)2 * L.H * L.F >= ((int64_t)1 << 20) || l->opt.implicit_small);   // (the data-efficient
                                 // net's 0.3 M-element layer: +0.8 us per step with the pairing — it pays from megabytes on)
     hw_.no_sigma = implicit_sigma ? 1 : 0;
     l->sigma_implicit = implicit_sigma ? 1 : 0;
@@ -2048,11 +2027,10 @@ static int learn_impl(rb_learner_t* l, const ImgSrc& src, const uint8_t* states_
     zx.out = l->dh; zx.ld_out = 2 * L.H; zx.mask_src = l->h;
     zx.dyT = l->dlogitsT; zx.ldyT = B; zx.outT = l->dhT;
     // the output layer's input gradient with eight waves per workgroup (noisy_linear.h rb_nl_dx_body_tall) at batch <= 32
-    // (RB_OPTS z_tall=0: the four-wave body)
-    const int z_tall = (l->opt_z_tall && B <= 32) ? 1 : 0;
-    // ... on 32-column tiles (RB_OPTS z_narrow=0: 64-column tiles): twice the workgroups, half the weight bytes through each CU
-    const int z_narrow = (z_tall && l->opt_z_narrow && (L.H % 32) == 0) ? 1 : 0;
-    NlBwdGrid zg{exch ? 0 : zp.dw_x, exch ? 0 : vt + at, (int)rb_div_up(L.H, z_narrow ? 32 : 64), 1, 2 * (int)rb_div_up(B, 64), z_tall ? z_narrow : (l->opt_z_deep ? 2 : 0)};
+    // on 32-column tiles (H % 32 == 0: fast_fc): twice the workgroups, half the weight bytes through each CU
+    const bool z_tall = B <= 32;
+    NlBwdGrid zg{exch ? 0 : zp.dw_x, exch ? 0 : vt + at, (int)rb_div_up(L.H, z_tall ? 32 : 64), 1, 2 * (int)rb_div_up(B, 64),
+                 z_tall ? RB_NL_DX_TALL : RB_NL_DX_M64_ST8};
     // ---- hidden layer
     NlDxArgs hx;
     hx.dy = l->dh; hx.ldy = 2 * L.H; hx.M = B; hx.w = nl_h(on); hx.K = L.F; hx.n_prob = 1;
@@ -2062,13 +2040,13 @@ static int learn_impl(rb_learner_t* l, const ImgSrc& src, const uint8_t* states_
     const int hsplits = (int)rb_div_up(2 * L.H, hx.rows_per_split);
     hx.out = l->dfeat_part; hx.ld_out = L.F; hx.mask_src = nullptr;
     hx.dyT = l->dhT; hx.ldyT = B; hx.outT = nullptr;
-    NlBwdGrid hg{exch ? 0 : hp.dw_x, exch ? 0 : hp.dw_y, (int)rb_div_up(L.F, 64), hsplits, (int)rb_div_up(B, 64), (B <= 32 && l->opt_h_deep) ? 1 : 0};
+    NlBwdGrid hg{exch ? 0 : hp.dw_x, exch ? 0 : hp.dw_y, (int)rb_div_up(L.F, 64), hsplits, (int)rb_div_up(B, 64), B <= 32 ? RB_NL_DX_M32_ST8 : RB_NL_DX_M64_ST4};
     NlPriorityUpdate up;
     memset(&up, 0, sizeof(up));
     // the write-back leaves this launch for the replay's stream (decided HERE, once: an expiry seen later only affects the next call)
     const bool spec = l->spec_now && l->sink && B <= 256 && !exch && rb_replay_spec_allowed(l->sink);
     if (l->sink && B <= 256 && !spec) {
-      up.enabled = l->opt_wb_auto ? 2 : 1; up.tree_idx = l->sink_idx; up.loss = loss_dev; up.n = B;
+      up.enabled = 1; up.tree_idx = l->sink_idx; up.loss = loss_dev; up.n = B;
       if (rb_replay_internal_view(l->sink, &up.view, &up.omega) != RB_OK) {
         rb_set_error("rb_learner_learn: bad priority sink");
         return RB_ERR_STATE;
@@ -2077,7 +2055,7 @@ static int learn_impl(rb_learner_t* l, const ImgSrc& src, const uint8_t* states_
     {
       NlPriorityUpdate none;
       memset(&none, 0, sizeof(none));
-      if (spec) { none.go_flag = l->opt_spec_stall ? nullptr : l->go_flag; none.go_epoch = ++l->go_epoch; }
+      if (spec) { none.go_flag = l->opt.spec_stall ? nullptr : l->go_flag; none.go_epoch = ++l->go_epoch; }
       const dim3 zgrid_((unsigned)(zg.dw_x * zg.dw_y + zg.dx_x * zg.dx_y * zg.dx_z));
       if (z_tall) { RB_LAUNCH_T("fc_z_bwd:k_nl_bwd", k_nl_bwd<true>, zgrid_, dim3(64 * RB_NL_DXT_WAVES), stream, zw, zx, zg, none); }
       else { RB_LAUNCH_T("fc_z_bwd:k_nl_bwd", k_nl_bwd<false>, zgrid_, dim3(256), stream, zw, zx, zg, none); }
@@ -2322,13 +2300,13 @@ static int train_step_impl(rb_learner_t* l, const rb_train_step_t* a, rb_comm_t*
   // would be launched now, outside the graph, waiting for a flag the captured kernels only store on replay.
   {
     auto& t = l->ts_last;
-    const bool capturing = l->opt_spec_draw && rb_stream_capturing(stream);
+    const bool capturing = l->opt.spec_draw && rb_stream_capturing(stream);
     const bool same = !capturing && t.valid && t.replay == a->replay && t.batch == a->batch && t.max_attempts == a->max_attempts &&
                       t.beta == a->priority_weight &&
                       t.tree_idx == a->tree_idx_dev && t.actions == a->actions_dev && t.returns == a->returns_dev &&
                       t.nonterm == a->nonterminals_dev && t.weights == a->weights_dev && t.mut_after == rb_replay_mutations(a->replay);
     t.streak = same ? t.streak + 1 : 0;
-    l->spec_now = (l->opt_spec_draw && t.streak >= 1 && comm == nullptr && a->noise_job != nullptr && a->batch <= 256 && l->fast_fc &&
+    l->spec_now = (l->opt.spec_draw && t.streak >= 1 && comm == nullptr && a->noise_job != nullptr && a->batch <= 256 && l->fast_fc &&
                    l->sink == a->replay && l->sink_idx == a->tree_idx_dev && rb_replay_spec_allowed(a->replay)) ? 1 : 0;
     if (l->spec_now) {
       rb_spec_request& q = l->spec_req;
@@ -2337,7 +2315,7 @@ static int train_step_impl(rb_learner_t* l, const rb_train_step_t* a, rb_comm_t*
       q.tree_idx = a->tree_idx_dev; q.actions = a->actions_dev; q.returns = a->returns_dev; q.nonterminals = a->nonterminals_dev;
       q.weights = a->weights_dev;
     }
-    if (l->opt_spec_draw && !capturing) rb_replay_spec_arm_accept(a->replay);     // only THIS caller reads the table of the accepted draw
+    if (l->opt.spec_draw && !capturing) rb_replay_spec_arm_accept(a->replay);     // only THIS caller reads the table of the accepted draw
   }
   int rc = rb_replay_sample_fused_noise(a->replay, a->batch, a->priority_weight, nullptr, a->max_attempts, a->tree_idx_dev, nullptr,
                                         nullptr, a->actions_dev, a->returns_dev, a->nonterminals_dev, a->weights_dev,
@@ -2670,9 +2648,9 @@ int rb_learner_finish_grads(rb_learner_t* l, rb_stream_t stream_) {
   }
   zp.a.eout_noff = L.z_eout; zp.a.ein_noff = L.z_ein;
   hp.a.eout_noff = L.h_eout; hp.a.ein_noff = L.h_ein;
-  // the hidden layer on 128 x 128 LDS tiles (fc_gemm.h rb_fc_gemm_dw_ranks; RB_OPTS finish_tiled=0: the 16-row-tile body): a
-  // rank's slab of the gathered factors is read once per 128 weight rows instead of once per 16
-  const bool tiled = l->opt_finish_tiled && 2 * L.H >= 64 && L.F >= 64;
+  // the hidden layer on 128 x 128 LDS tiles (fc_gemm.h rb_fc_gemm_dw_ranks): a rank's slab of the gathered factors is read once
+  // per 128 weight rows instead of once per 16 (narrower layers: the 16-row-tile body)
+  const bool tiled = 2 * L.H >= 64 && L.F >= 64;
   const int h_nt = (int)rb_div_up(2 * L.H, RB_TG_T), h_kt = (int)rb_div_up(L.F, RB_TG_T);
   if (tiled) {
     // (every workgroup of this launch is 512 threads at ~250 registers: ONE per CU.  The output layer's tiles therefore take all

@@ -170,12 +170,8 @@ __global__ __launch_bounds__(64 * RB_NL_FWD_WAVES) void k_nl_fwd3(NlFwd2Args a) 
   // EXACT: no ring slot is ever loaded with a block past the wave's range (round 6: the clamped duplicates — the output layer's 2 blocks
   // per wave in a ring of 4, the 3-4 refills of the hidden layer's last round — were a fifth to a half of what a workgroup pulled
   // through its CU: fc_h 15.7 -> 15.0 us, fc_z 6.1 -> 5.1 us; the 64-row form of batch 256 measured 1 us slower with it and keeps the
-  // clamped loads, as does an -DRB_FWD_CLAMPED_REFILLS build)
-#if defined(RB_FWD_CLAMPED_REFILLS)
-  constexpr bool EXACT = false;
-#else
+  // clamped loads)
   constexpr bool EXACT = MT <= 2;
-#endif
 #pragma unroll
   for (int d = 0; d < RING; ++d) {
     if (!EXACT) { load_w(d, blk_of(d)); load_x(d, blk_of(d)); }
@@ -255,11 +251,7 @@ __global__ __launch_bounds__(64 * RB_NL_FWD_WAVES) void k_nl_fwd3(NlFwd2Args a) 
     const int m = m0 + 16 * mt + 4 * (l >> 4) + e;
     const int n = row0 + (l & 15);
     if (m < M && m < m0 + 16 * MT && n < row_end) {
-#if defined(RB_NO_BIAS_PRE)                                                 // (A/B build: the loads in the epilogue)
-      float o = v + (w.bmu[n] + w.bsigma[n] * w.eout[n]);
-#else
       float o = v + (b_mu + b_sg * b_eo);                                 // model.py:44 (n == nb_ for every cell that is stored)
-#endif
       if (a.relu) o = fmaxf(o, 0.0f);
       const int rowi = a.m_base[net] + m;
       a.out[(int64_t)rowi * a.ld_out + n] = o;
@@ -299,7 +291,7 @@ struct NlDxArgs {
 // grid = (64-column tiles, row splits, n_prob * m-chunks of 64), block = 256 (4 waves split the rows)
 #define RB_NL_DX_LDS (2 * 64 * 64)   // floats: two wave tiles (the four waves meet pairwise, see the reduction below)
 // MTC = 16-row m tiles a workgroup can hold (4: 64-row m-chunks; 2: batches of <= 32 — half the accumulators), ST = row-steps of 4
-// weight rows whose loads are in flight together.  <2, 8> (RB_OPTS h_deep, batch <= 32): a wave's 64 rows are TWO dependent load ->
+// weight rows whose loads are in flight together.  <2, 8> (batch <= 32): a wave's 64 rows are TWO dependent load ->
 // MFMA trips instead of four (round6_wg_timeline_b32.txt: first trip 4.6 us, the three behind it 6.4 of the workgroup's 14.6) —
 // the rows enter the accumulators in the same order: an element's bits do not depend on ST.
 template <int MTC, int ST>
@@ -453,8 +445,8 @@ __device__ __forceinline__ void rb_nl_dx_body(const NlDxArgs& a, int bx, int by,
 #define RB_NL_DXT_LDS (RB_NL_DXT_WAVES * 32 * 64)
 // CW = columns per lane: 4 = 64-column tiles (16-byte loads), 2 = 32-column tiles (8-byte loads, still one whole 128-byte line per
 // weight row and row-step: twice the workgroups at half the bytes each — the advantage stream's 64-column workgroup pulls 157 KB
-// of mu | sigma through ONE CU, 8.0 us against the value stream's 5.3; RB_OPTS z_narrow).  Same rows per wave, same wave-order sum:
-// an element's value does not depend on CW.
+// of mu | sigma through ONE CU, 8.0 us against the value stream's 5.3).  Same rows per wave, same wave-order sum:
+// an element's value does not depend on CW.  Every hidden size the streamed kernels accept is a multiple of 32: only CW = 2 runs.
 template <int CW>
 struct RbVec;
 template <> struct RbVec<4> { typedef float4 T; };
@@ -607,8 +599,8 @@ struct NlDwArgs {
   const float *eout, *ein;
   float* sq_part;            // optional: one slot per (block, wave) receiving the sum of squares of what that wave wrote
                              // (feeds clip_grad_norm_ without another pass over the 27 MB gradient)
-  int deep;                  // ct == 4: every tile's operands in flight before the first MFMA (rb_nl_dw_body_pipe_all)
-  int ct;                    // > 0: pipelined body, `ct` column tiles per wave (M <= 32); 0: one tile per wave;
+  int ct;                    // > 0: pipelined body, `ct` column tiles per wave (M <= 32; 4: every tile's operands in flight before
+                             // the first MFMA, rb_nl_dw_body_pipe_all); 0: one tile per wave;
                              // < 0: the LDS-shared 64 x 64 tile body for large M (rb_nl_dw_body_wide)
   int no_sigma;              // 1: g_sigma is formed for the sum of squares only and NOT stored (the hosted optimiser pass forms it
                              // again from g_mu and the same noise, adam_body.h; pipelined body only)
@@ -691,10 +683,6 @@ __device__ __forceinline__ void rb_nl_dw_body(const NlDwArgs& a, int bx, int by,
   {
     float avs0[8], avs1[8];
     float4 xs0[8], xs1[8];
-#if defined(RB_DW_NOPRE)                                   // (A/B build: one trip at a time)
-    for (int mb = 0; mb < a.M; mb += 32) { issue(mb, avs0, xs0); mfmas(mb, avs0, xs0); }
-    (void)avs1; (void)xs1;
-#else
     issue(0, avs0, xs0);
     for (int mb = 0; mb < a.M; mb += 64) {
       const bool second = mb + 32 < a.M;                   // uniform
@@ -705,7 +693,6 @@ __device__ __forceinline__ void rb_nl_dw_body(const NlDwArgs& a, int bx, int by,
         mfmas(mb + 32, avs1, xs1);
       }
     }
-#endif
   }
   float sq = 0.0f;
 #pragma unroll
@@ -948,7 +935,7 @@ __device__ __forceinline__ void rb_nl_dw_body_pipe(const NlDwArgs& a, int bx, in
     if (lane == 0) a.sq_part[slot_base + wave] = sq;
   }
 }
-// ... with the operands of ALL CT column tiles of a wave requested before the first MFMA (RB_OPTS h_dw_deep): the one-tile-ahead
+// ... with the operands of ALL CT column tiles of a wave requested before the first MFMA (ct == 4): the one-tile-ahead
 // form above turns a tile every ~3.3 us (13.2 us for the hidden layer's four: a round trip beside the launch's 39 MB is longer than
 // a tile's 40 MFMAs), this one pays the trip once.  Same tiles, same order inside a tile: bit-identical gradients and norm partials.
 template <int CT>
@@ -1054,12 +1041,14 @@ __device__ __forceinline__ void rb_nl_dw_body_pipe_all(const NlDwArgs& a, int bx
 // Horizontal fusion: the weight-gradient and the input-gradient of one layer are independent given dY, so both run in
 // ONE launch (one ~5 us kernel boundary less on the critical path).  Blocks [0, dw_x*dw_y) take the dW tiles, the rest
 // the dX tiles.
-struct NlBwdGrid { int dw_x, dw_y, dx_x, dx_y, dx_z; int dx_narrow; };   // dx_narrow: TALL: 32-column input-gradient tiles; else: 1 = rb_nl_dx_body<2, 8> (batch <= 32), 2 = <4, 8>: deep loads
+// the input-gradient body of a launch: rb_nl_dx_body<4, 4> | <2, 8> (batch <= 32) | <4, 8>; k_nl_bwd<TALL>: rb_nl_dx_body_tall<2>
+enum NlDxBody { RB_NL_DX_M64_ST4, RB_NL_DX_M32_ST8, RB_NL_DX_M64_ST8, RB_NL_DX_TALL };
+struct NlBwdGrid { int dw_x, dw_y, dx_x, dx_y, dx_z; int dx_body; };
 // Optional third tenant of the output layer's backward launch: the sum-tree priority write-back (agent.py:100,
 // memory.py:157-159).  It depends only on (tree indices, per-sample loss), both final before this launch, and is a
 // single-workgroup latency chain — as one more block here it costs nothing on the step's critical path.
 struct NlPriorityUpdate {
-  int enabled;
+  int enabled;               // 0 / 1
   ReplayView view;
   const int64_t* tree_idx;
   const float* loss;
@@ -1109,14 +1098,10 @@ __global__ __launch_bounds__(TALL ? 64 * RB_NL_DXT_WAVES : 256) void k_nl_bwd(Nl
     if (TALL && threadIdx.x >= 256 && b == 0) return;    // (the write-back body is written for 256 threads)
     if (b == 0) {
       RB_SPAN_BEGIN(sb + 0);
-      // (the one-wave sorted write-back of k_update measured no faster HERE — same-box A/B of two builds on all three configs:
-      // 160.9 / 103.5 / 498.5 against 161.4 / 103.0 / 497.8 us per step — this block is not the launch's long pole)
-      // enabled == 2 (RB_OPTS wb_auto, default): a sorted batch of <= 64 leaves — what the sampler hands back — on ONE wave without LDS
-      // tables or workgroup barriers (rb_update_sorted_wave), anything else through the hashed body.  Round 4 measured no gain from it
-      // HERE, when the input-gradient tiles were this launch's pole; since round 6's deeper bodies the write-back is (17.0 us hashed,
-      // round6_final_wg_timeline_b32.txt).  Same tree, bit for bit, either way.
-      if (up.enabled == 2) rb_update_auto<512, 256>(up.view, up.tree_idx, up.loss, up.n, 1, up.omega, lds);   // block-uniform
-      else rb_update_body<512, 256>(up.view, up.tree_idx, up.loss, up.n, 1, up.omega, lds);     // n <= 256
+      // a sorted batch of <= 64 leaves — what the sampler hands back — on ONE wave without LDS tables or workgroup barriers
+      // (rb_update_sorted_wave), anything else through the hashed body (17.0 us and this launch's pole, round6_final_wg_timeline_b32.txt).
+      // Same tree, bit for bit, either way.
+      rb_update_auto<512, 256>(up.view, up.tree_idx, up.loss, up.n, 1, up.omega, lds);     // n <= 256
       RB_SPAN_END(sb + 0);
       RB_WGT_ROLE(kid, wgb, 0);
       RB_WGT(kid, wgb, 6);
@@ -1129,7 +1114,7 @@ __global__ __launch_bounds__(TALL ? 64 * RB_NL_DXT_WAVES : 256) void k_nl_bwd(Nl
     if (TALL && threadIdx.x >= 256) return;              // the weight-gradient bodies are 4-wave bodies (their barriers count
                                                          // the waves that are still alive)
     RB_SPAN_BEGIN(sb + 1);
-    if (dw.ct == 4 && dw.deep) rb_nl_dw_body_pipe_all<4>(dw, b % g.dw_x, b / g.dw_x, 4 * b);     // block-uniform
+    if (dw.ct == 4) rb_nl_dw_body_pipe_all<4>(dw, b % g.dw_x, b / g.dw_x, 4 * b);     // block-uniform
     else if (dw.ct > 0) rb_nl_dw_body_pipe(dw, b % g.dw_x, b / g.dw_x, 4 * b);
     else rb_nl_dw_body(dw, b % g.dw_x, b / g.dw_x, 4 * b);
     RB_SPAN_END(sb + 1);
@@ -1138,11 +1123,10 @@ __global__ __launch_bounds__(TALL ? 64 * RB_NL_DXT_WAVES : 256) void k_nl_bwd(Nl
     const int r = b - ndw;
     RB_SPAN_BEGIN(sb + 2);
     if constexpr (TALL) {
-      if (g.dx_narrow) rb_nl_dx_body_tall<2>(dx, r % g.dx_x, r / g.dx_x, lds);      // block-uniform
-      else rb_nl_dx_body_tall<4>(dx, r % g.dx_x, r / g.dx_x, lds);
+      rb_nl_dx_body_tall<2>(dx, r % g.dx_x, r / g.dx_x, lds);
     }
-    else if (g.dx_narrow == 2) rb_nl_dx_body<4, 8>(dx, r % g.dx_x, (r / g.dx_x) % g.dx_y, r / (g.dx_x * g.dx_y), lds);   // block-uniform
-    else if (g.dx_narrow) rb_nl_dx_body<2, 8>(dx, r % g.dx_x, (r / g.dx_x) % g.dx_y, r / (g.dx_x * g.dx_y), lds);
+    else if (g.dx_body == RB_NL_DX_M64_ST8) rb_nl_dx_body<4, 8>(dx, r % g.dx_x, (r / g.dx_x) % g.dx_y, r / (g.dx_x * g.dx_y), lds);   // block-uniform
+    else if (g.dx_body == RB_NL_DX_M32_ST8) rb_nl_dx_body<2, 8>(dx, r % g.dx_x, (r / g.dx_x) % g.dx_y, r / (g.dx_x * g.dx_y), lds);
     else rb_nl_dx_body<4, 4>(dx, r % g.dx_x, (r / g.dx_x) % g.dx_y, r / (g.dx_x * g.dx_y), lds);
     RB_SPAN_END(sb + 2);
     RB_WGT_ROLE(kid, wgb, 2);

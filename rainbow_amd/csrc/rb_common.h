@@ -55,10 +55,6 @@ static inline bool rb_stream_capturing(void* stream) {
 #endif
 }
 
-// ---- RB_OPTS="key=value,key=value": the library's ONE tuning / test-hook variable (common.hip; DESIGN.md §8 lists the keys).
-// Returns `dflt` when the key is absent.  Read when a handle is created, never per launch.
-int rb_opt(const char* key, int dflt);
-
 // ---- Philox4x32-10 counter RNG (device sampler + noise) ------------------------------
 struct rb_philox_out {
   uint32_t v[4];

@@ -139,13 +139,11 @@ __device__ __forceinline__ void rb_chain_wait(const unsigned* counter, unsigned 
 #endif
 }
 
-// The same hand-off for ALL-TO-ALL boundaries of a persistent launch (every workgroup arrives, every workgroup waits): one
-// counter serialises its arrivals at ~12 ns each (256 workgroups: 3.3-4.4 us per boundary, tools/stamp/act_timeline.py), so
-// the arrivals are SHARDED over 8 counters in 8 different 128-byte lines (shard = workgroup index mod 8, i.e. its XCD) and a
-// waiter reads all eight in one batch.  `counters` = the boundary's 8 x 32 words; per_shard = arrivals per shard and launch.
-#ifndef RB_FAN_SHARDS
-#define RB_FAN_SHARDS 32           // (8 until round 6: with 256 producers — the hidden layer's phase — 32 arrivals per line still took 3 us)
-#endif
+// The same hand-off for the phase boundaries of a persistent launch (many workgroups arrive, many wait): one counter serialises
+// its arrivals at ~12 ns each (256 workgroups: 3.3-4.4 us per boundary, tools/stamp/act_timeline.py), so the arrivals are
+// SHARDED over RB_FAN_SHARDS counters in as many 128-byte lines (shard = workgroup index mod RB_FAN_SHARDS) and a waiter reads
+// all of them in one batch.  `counters` = the boundary's RB_FAN_SHARDS x RB_FAN_STRIDE words.
+#define RB_FAN_SHARDS 32           // (with 8 shards and 256 producers — the hidden layer's phase — 32 arrivals per line still took 3 us)
 #define RB_FAN_STRIDE 32            // words between shards (128 bytes)
 __device__ __forceinline__ void rb_fan_signal(unsigned* counters, int wg) {           // all threads of the workgroup call
 #if defined(RB_HOST_INTERP)
@@ -157,29 +155,10 @@ __device__ __forceinline__ void rb_fan_signal(unsigned* counters, int wg) {     
   if (threadIdx.x == 0) __hip_atomic_fetch_add(counters + (wg % RB_FAN_SHARDS) * RB_FAN_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
 }
-// err_tag: what an expired wait stores into *err (the launch number: the reader compares with its own, so one failed launch
-// does not poison the next)
-__device__ __forceinline__ void rb_fan_wait(const unsigned* counters, unsigned target_per_shard, unsigned* err, unsigned err_tag = 1u) {   // all threads call
-#if defined(RB_HOST_INTERP)
-  __syncthreads();                                                          // (one launch per phase there: nothing to wait for)
-  (void)counters; (void)target_per_shard; (void)err; (void)err_tag;
-#else
-  if (threadIdx.x < 64) {                                                   // wave 0: lane s polls shard s
-    const int lane = (int)threadIdx.x;
-    unsigned spins = 0;
-    for (;;) {
-      unsigned v = target_per_shard;
-      if (lane < RB_FAN_SHARDS) v = __hip_atomic_load(counters + lane * RB_FAN_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__all((int)(v - target_per_shard) >= 0)) break;
-      __builtin_amdgcn_s_sleep(2);
-      if (++spins > (1u << 22)) { if (lane == 0) __hip_atomic_store(err, err_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-    }
-  }
-  __syncthreads();
-#endif
-}
-// The same wait where only the workgroups [0, producers) of the launch arrive at this boundary (shard = index mod 8, so shard s
-// gets (producers - s + 7) / 8 arrivals per launch): `launches` = this launch's number, counters monotonic as above.
+// The wait: only the workgroups [0, producers) of the launch arrive at this boundary (shard = index mod RB_FAN_SHARDS, so shard s
+// gets (producers - s + RB_FAN_SHARDS - 1) / RB_FAN_SHARDS arrivals per launch); wave 0 polls, lane s shard s.  `launches` = this
+// launch's number, counters monotonic.  err_tag: what an expired wait stores into *err (the launch number: the reader compares
+// with its own, so one failed launch does not poison the next)
 __device__ __forceinline__ void rb_fan_wait_first(const unsigned* counters, unsigned launches, int producers, unsigned* err, unsigned err_tag = 1u) {   // all threads call
 #if defined(RB_HOST_INTERP)
   __syncthreads();

@@ -406,17 +406,6 @@ __device__ __forceinline__ void rb_descend_levels(const float* tree, int32_t& no
   // at batch 256 the address unit, not the latency, set the length of a trip (15 us per trip beside the optimiser stream, 6.6 at
   // batch 32).  An entry beyond the last node reads as tree[last] (the clamp above); the vectors themselves start at
   // min(base, last) and may run up to 2^D - 1 entries past the end: the tree buffer is padded for that (RB_TREE_PAD).
-#if defined(RB_DESC_SCALAR)      // (variant build for A/B runs: one clamped dword load per entry, the form up to round 5)
-#pragma unroll
-  for (int j = 1; j <= D; ++j) {
-    const uint32_t base = (((uint32_t)node + 1u) << j) - 1u;
-#pragma unroll
-    for (int t = 0; t < (1 << j); ++t) {
-      const uint32_t q = base + (uint32_t)t;
-      c[(1 << j) - 2 + t] = tree[q > (uint32_t)last ? (uint32_t)last : q];
-    }
-  }
-#else
   const float t_last = tree[last];
 #pragma unroll
   for (int j = 1; j <= D; ++j) {
@@ -438,7 +427,6 @@ __device__ __forceinline__ void rb_descend_levels(const float* tree, int32_t& no
       }
     }
   }
-#endif
   int sel = 0;
 #pragma unroll
   for (int j = 1; j <= D; ++j) {
@@ -613,13 +601,10 @@ __device__ long long g_stamp[32];
 // AU = float4 quadruples per thread of the hosted optimiser workgroups (adam_body.h): they inherit this kernel's register
 // allocation, i.e. 2 waves per SIMD under the 256-thread variant's 205 VGPRs (needs AU = 8 to keep enough bytes in flight:
 // 42 us per hosted launch against 46 with AU = 4) and 4 under the 1024-thread variant's 127 (AU = 4)
-#ifndef RB_HOST_AU_WIDE
 #define RB_HOST_AU_WIDE 4      // quadruples per hosted thread under the 1024-thread variant (5 spills under its 128-register cap)
-#endif
-// learner.hip sizes the pending pass for 4 quadruples per plain thread and 2 (mu, sigma) pairs per pair thread (pair_blk0 and
-// the pair grid in clip_adam_impl); the hosting launch rescales the block count by this constant — any other value would split
-// plain and pair workgroups differently from what the pass expects (parameters skipped or updated twice)
-static_assert(RB_HOST_AU_WIDE == 4, "the hosted optimiser pass is laid out for 4 quadruples per thread (learner.hip clip_adam_impl)");
+// (learner.hip sizes the pending pass for 4 quadruples per plain thread and 2 (mu, sigma) pairs per pair thread — pair_blk0 and
+// the pair grid in clip_adam_impl; the hosting launch rescales the block count by this constant: any other value would split
+// plain and pair workgroups differently from what the pass expects)
 template <int MAXT>
 __device__ __forceinline__ void rb_sample_main(const ReplayView& v, int32_t batch, float neg_beta_arg, const float* neg_beta_ptr,
                                                const double* unit_uniforms, int32_t max_attempts, uint64_t seed, const float* scaling,

@@ -63,12 +63,12 @@ def test_chunk_fastest_conv_block_order_matches_golden(emu, monkeypatch):
     ad.close()
 
 
-@pytest.mark.parametrize("t16", ["0", "6"], ids=["split-k-32x32", "whole-k-16x16-later-layers-only"])
+@pytest.mark.parametrize("t16", ["0"], ids=["whole-k-16x16-later-layers-only"])
 def test_conv_forward_tile_variants_match_golden(emu, monkeypatch, t16):
     """The conv forward's MFMA phase exists twice (conv_lds.h rb_conv_fwd_body): 32x32x2 tiles with the reduction split over 8
     waves + an LDS sum, and (T16) one wave per 16x16 tile over the whole reduction with the epilogue straight from the
-    accumulators.  Default: T16 for every layer incl. the u8 first one (RB_OPTS t16=7, what every other test runs); here all layers
-    on the split-K body (t16=0) and the first layer alone on it (t16=6)."""
+    accumulators.  Default: T16 for every canonical layer incl. the u8 first one (what every other test runs); RB_OPTS t16=0 puts
+    the first layer alone on the split-K kernel — what a canonical network with history < 4 runs — on the history-4 fixture."""
     monkeypatch.setenv("RB_OPTS", "t16=" + t16)
     name = "canon"
     ad = CAbiLearnAdapter(emu, NumpyMem(), name)
@@ -79,23 +79,48 @@ def test_conv_forward_tile_variants_match_golden(emu, monkeypatch, t16):
     ad.close()
 
 
-@pytest.mark.parametrize("name,steps,full,t16", [("dataeff", None, "1", 1), ("canon", 1, "1", 1), ("canon", 1, "0", 1), ("canon", 1, "1", 0)])
-def test_multi_image_conv_kernels_match_golden(emu, monkeypatch, name, steps, full, t16):
+@pytest.mark.parametrize("name,steps,full", [("dataeff", None, "1"), ("canon", 1, "1"), ("canon", 1, "0")],
+                         ids=["dataeff-None-1-1", "canon-1-1-1", "canon-1-0-1"])
+def test_multi_image_conv_kernels_match_golden(emu, monkeypatch, name, steps, full):
     """Large batches run the conv forward and data-gradient kernels with one weight slab per workgroup and a loop over
-    images (k_conv_fwd_multi_t16 / k_conv_dx_t16_multi — whole-K 16x16x4 tiles, round 6 — or, t16 = 0, the split-K k_conv_fwd_multi /
-    k_conv_dx_lds<..., MULTI>); RB_OPTS conv_multi / dx_ipb force those paths (ragged: neither divides the batch; the group of 5
-    that holds the last online and the first target image re-stages its slab) on the small fixtures, with the last layer's dY
+    images (canonical later layers: k_conv_fwd_multi_t16 / k_conv_dx_t16_multi, whole-K 16x16x4 tiles; the data-efficient second
+    layer: k_conv_dx_lds<..., MULTI>); RB_OPTS conv_multi / dx_ipb force those paths (ragged: neither divides the batch; the group
+    of 5 that holds the last online and the first target image re-stages its slab) on the small fixtures, with the last layer's dY
     formed from the row-split partials in the loop."""
     # dx_ipb / conv_multi: ragged image groups in the input-gradient and forward kernels; conv_full: the first layer's
     # whole-image kernel (k_conv_fwd_full) or, 0, the one-image kernel
-    # (t16 = 0: the split-K bodies of both the forward and the data gradient; 1: k_conv_fwd_multi_t16 / k_conv_dx_t16_multi)
     # dw_ipb<layer>: images summed per workgroup of the weight-gradient launch, chosen per layer at large batches (ragged here too)
-    monkeypatch.setenv("RB_OPTS", "dx_ipb=3,conv_multi=5,conv_full=%s,conv_multi_t16=%d,dx_t16=%d,dw_ipb0=3,dw_ipb1=2,dw_ipb2=5" % (full, t16, t16))
+    monkeypatch.setenv("RB_OPTS", "dx_ipb=3,conv_multi=5,conv_full=%s,dw_ipb0=3,dw_ipb1=2,dw_ipb2=5" % full)
     ad = CAbiLearnAdapter(emu, NumpyMem(), name)
     trace = scenarios.learn_scenario(ad, name, O, steps=steps)
     golden = load_golden("learn_%s.npz" % name)
     assert_learn_trace_matches(trace, {k: v for k, v in golden.items() if k in trace}, label="emu-dx-multi/" + name)
     assert any("_grad/convs.0" in k for k in trace)
+    ad.close()
+
+
+RB_OPTS_DEFAULTS = ("generic=0,fc_gemm=-1,implicit_small=0,xs=0,act_fused=1,spec_draw=0,spec_stall=0,img_fast=1,conv_multi=-1,"
+                    "conv_full=1,t16=1,dx_ipb=0,dw_ipb0=0,dw_ipb1=0,dw_ipb2=0")
+
+
+@pytest.mark.parametrize("opts", ["z_narrow=0", "nonsense=1", "spec_draw", "xs=", "img_fast=0,dx_t16=0"])
+def test_rb_opts_rejects_unknown_and_malformed_entries(emu, monkeypatch, opts):
+    """A key that rb_learner_create does not know (a typo, a retired switch) or an entry without '=value' fails the call and
+    rb_last_error() names it (here: the key of the last entry): an A/B run can no longer silently measure the default."""
+    key = opts.split(",")[-1].split("=")[0]
+    monkeypatch.setenv("RB_OPTS", opts)
+    with pytest.raises(RuntimeError) as e:
+        CAbiLearnAdapter(emu, NumpyMem(), "atoms21")
+    assert "RB_OPTS" in str(e.value) and "'%s'" % key in str(e.value)
+
+
+def test_rb_opts_every_key_at_its_default_is_the_default(emu, monkeypatch):
+    """Every key of the option table spelled out at its default value: the golden trace of the default configuration."""
+    monkeypatch.setenv("RB_OPTS", RB_OPTS_DEFAULTS)
+    name = "dataeff"
+    ad = CAbiLearnAdapter(emu, NumpyMem(), name)
+    trace = scenarios.learn_scenario(ad, name, O)
+    assert_learn_trace_matches(trace, load_golden("learn_%s.npz" % name), label="emu-opts-defaults/" + name)
     ad.close()
 
 
