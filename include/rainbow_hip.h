@@ -132,6 +132,34 @@ int rb_replay_header(rb_replay_t* r, rb_replay_header_t* out_host, rb_stream_t s
 int rb_frame_preprocess(const uint8_t* frame_a_dev, const uint8_t* frame_b_dev, int32_t height, int32_t width, int32_t n,
                         float* out_dev, rb_stream_t stream);
 
+/* The observation front end of S host emulators (env.py's wrapper around ALE) for all S streams in ONE launch per round:
+ * the resize and frame max of rb_frame_preprocess plus the state deque (env.py:24,68,77), its blanking at a true reset
+ * (env.py:31-33,41), the life-loss reset that must not blank (env.py:36-38,49-52) and the truncated action repeat
+ * (env.py:56-67: a frame of the pair that was never taken stays zero).  Stateless, like rb_frame_preprocess.
+ * frames_a_dev / frames_b_dev: u8 [streams][height][width] each (the screens after frames 3 and 4 of the repeat); either may
+ * be NULL when no stream's flags name it.  stacks_in_dev / stacks_out_dev: f32 [streams][history][84][84], oldest frame first,
+ * 16-byte aligned, out of place (they must not overlap) — the layout rb_learner_act_batch and rb_replay_append_streams* take.
+ * flags_host: `streams` bytes of host memory, passed to the kernel by value (reusable when the call returns); per stream a
+ * bit set of RB_OBS_*.  All eight values are defined:
+ *  - frames 0 .. history-2 of the output are frames 1 .. history-1 of the input, or all zeros if RB_OBS_BLANK is set;
+ *  - frame history-1 of the output is the element-wise max over the PRESENT frames (RB_OBS_FRAME_A, RB_OBS_FRAME_B) of
+ *    resize(frame) / 255 — bit-identical to rb_frame_preprocess on the same screens — or zeros if neither is present.
+ * What each value stands for in env.py:
+ *    FRAME_A | FRAME_B (6)   step(), the whole repeat ran (env.py:58-68)
+ *    BLANK | FRAME_A   (3)   reset() of a new game (env.py:40-52)
+ *    FRAME_A           (2)   reset() after a lost life: one no-op, no blanking (env.py:36-38,49-52); also step() whose
+ *                            repeat was cut after its third frame (env.py:60-61,65-66)
+ *    0                       step() whose repeat was cut before its third frame (env.py:56,65-67: both frames zero)
+ * Refused with RB_ERR_INVALID and a message that names the argument: NULL or misaligned or overlapping stacks, NULL
+ * flags_host, streams outside [1, 64], history outside [1, 16], height or width outside [2, 4096], a flag byte above 7, a
+ * flag that names a frame whose pointer is NULL.  Same PARITY UNPINNED caveat as rb_frame_preprocess.                       */
+#define RB_OBS_BLANK 1
+#define RB_OBS_FRAME_A 2
+#define RB_OBS_FRAME_B 4
+int rb_obs_stack_step(const uint8_t* frames_a_dev, const uint8_t* frames_b_dev, int32_t height, int32_t width, int32_t streams,
+                      int32_t history, const uint8_t* flags_host, const float* stacks_in_dev, float* stacks_out_dev,
+                      rb_stream_t stream);
+
 /* ReplayMemory.append (memory.py:105-108) + SegmentTree.append (memory.py:56-61):
  * quantises state_dev[history-1] (f32 in [0,1]) to u8 by x*255 truncation ON DEVICE,
  * stores (timestep, frame, action, reward, nonterminal) at `index`, sets the leaf to

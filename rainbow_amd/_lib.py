@@ -76,6 +76,7 @@ SIGNATURES = {
     "rb_replay_buffers": (c_int, [c_void_p, C.POINTER(ReplayBuffers)]),
     "rb_replay_header": (c_int, [c_void_p, C.POINTER(ReplayHeader), c_void_p]),
     "rb_frame_preprocess": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "rb_obs_stack_step": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rb_replay_append": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_int32, c_void_p]),
     "rb_replay_append_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "rb_replay_append_streams": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -169,6 +170,7 @@ def declare(lib, strict=True):
 
 
 LEARNER_FUSE_FC_H_DW, LEARNER_WRITE_FUSED_GRADS, LEARNER_DEFER_UPDATE, LEARNER_IMPLICIT_SIGMA = 1, 2, 4, 8
+OBS_BLANK, OBS_FRAME_A, OBS_FRAME_B = 1, 2, 4          # RB_OBS_* (rb_obs_stack_step)
 
 
 class RainbowError(RuntimeError):

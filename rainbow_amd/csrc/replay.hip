@@ -250,27 +250,7 @@ __global__ __launch_bounds__(256) void k_append_streams(ReplayView v, const floa
 // The resize is OpenCV's 8-bit fixed-point INTER_LINEAR (11-bit coefficients; oracle/frame_oracle.py has the algebra and
 // says why this row is parity-UNPINNED: cv2 is absent here).  One thread per output pixel; the taps of a pixel are four
 // bytes per frame, the coefficients two float operations — nothing worth staging.
-__device__ __forceinline__ void rb_resize_tap(int d, int dst, int src, bool clamp_f, int* s_out, int* c0, int* c1) {
-  const double scale = (double)src / (double)dst;
-  float f = (float)__dsub_rn(__dmul_rn((double)d + 0.5, scale), 0.5);          // float((d + 0.5) * scale - 0.5)
-  int s = (int)floorf(f);
-  f = __fsub_rn(f, (float)s);
-  if (clamp_f) {
-    if (s < 0) { f = 0.0f; s = 0; }
-    if (s >= src - 1) { f = 0.0f; s = src - 1; }
-  }
-  *s_out = s;
-  *c0 = __float2int_rn(__fmul_rn(__fsub_rn(1.0f, f), 2048.0f));               // saturate_cast<short>(cbuf * INTER_RESIZE_COEF_SCALE)
-  *c1 = __float2int_rn(__fmul_rn(f, 2048.0f));
-}
-__device__ __forceinline__ int rb_resize_pixel(const uint8_t* img, int H, int W, int sx, int a0, int a1, int sy, int b0, int b1) {
-  const int x1 = sx + 1 < W ? sx + 1 : W - 1;
-  const int y0 = sy < 0 ? 0 : (sy > H - 1 ? H - 1 : sy);
-  const int y1 = sy + 1 < 0 ? 0 : (sy + 1 > H - 1 ? H - 1 : sy + 1);
-  const int h0 = (int)img[(int64_t)y0 * W + sx] * a0 + (int)img[(int64_t)y0 * W + x1] * a1;
-  const int h1 = (int)img[(int64_t)y1 * W + sx] * a0 + (int)img[(int64_t)y1 * W + x1] * a1;
-  return ((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16)) + 2) >> 2;
-}
+#include "obs_stack.h"   // rb_resize_tap / rb_resize_pixel, and the S-stream frame-stack front end (rb_obs_stack_step)
 __global__ __launch_bounds__(256) void k_frame_preprocess(const uint8_t* a, const uint8_t* b, int H, int W, int n_pairs,
                                                            int64_t pair_stride, float* out) {
   const int pair = (int)blockIdx.y;

@@ -3,7 +3,11 @@
 A round is launches on one stream and nothing else: Agent.act_batch(device_out=True) -> env.step_device ->
 ReplayMemory.append_streams with device operands -> Agent.learn.  Actions, rewards, nonterminals and the per-stream episode
 timesteps never reach the host, and no call in a round synchronises (Agent.learn reports a sampler that found no batch one
-call late, from pinned memory).  `env` is a rainbow_amd.envs environment (CatchVec) with as many streams as `mem`."""
+call late, from pinned memory).  `env` is a rainbow_amd.envs environment (CatchVec) with as many streams as `mem`.
+
+`train_host_vec` is the same loop for S raw HOST emulators (ALE) behind a rainbow_amd.frames.FrameStackVec: the emulators write
+their u8 screens into the front end's pinned staging, one upload and one launch per round build all S frame stacks."""
+import numpy as np
 import torch
 
 
@@ -34,6 +38,68 @@ def train_device(agent, mem, env, args, T_max, on_eval=None):
         if clip_needed:
             rewards = rewards.clamp(-clip, clip)                                  # main.py:155-156
         mem.append_streams(states, actions, rewards, nonterminals=nonterminals)   # main.py:157
+        if T >= args.learn_start:
+            mem.priority_weight = min(mem.priority_weight + increase * S, 1)      # main.py:161
+            learn_owed += S / args.replay_frequency
+            while learn_owed >= 1:
+                agent.learn(mem)                                                  # main.py:164
+                learn_owed -= 1
+                learns += 1
+            if on_eval is not None and eval_every and T % eval_every < S:         # main.py:166-170
+                on_eval(T)
+                agent.train()
+            if T % args.target_update < S:
+                agent.update_target_net()                                         # main.py:177-178
+        states = next_states
+    return learns
+
+
+def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None):
+    """main.py:146-184 for S = len(emus) raw host emulators behind `front`, a rainbow_amd.frames.FrameStackVec (INTEGRATION.md
+    §2).  emus[s] is duck-typed:
+        reset(out_a)                 starts the next game — or, after a step that reported life_lost, does env.py:36-38's
+                                     single no-op instead — and writes the u8 [H, W] screen into out_a
+        step(action, out_a, out_b)   env.py:54-75: repeats the action, writes the screens after frames 3 and 4 of the repeat
+                                     into out_a / out_b as far as the repeat got, and returns (flags, reward, done, life_lost):
+                                     flags = the FrameStackVec bits of the frames it wrote, done = the game is over,
+                                     life_lost = a life was lost and the game goes on (env.py:70-75, training mode)
+    A stream whose step ended its game is reset in the same round and its next stack is the RESET stack (env.py:40-52), as
+    rainbow_amd.envs.CatchVec does; a stream that lost a life gets LIFE_RESET from the emulator's no-op screen.  Either way the
+    transition is stored as terminal and the observation of the ending step itself is never stored by the replay (it is not
+    in the reference either: memory.py:105-108 stores state[-1] of the state acted on).  One difference to env.py remains for
+    the ACTOR: after a lost life env.py's deque also holds the ending step's observation below the no-op screen, here the
+    stream's stack moves by one frame per round, so that frame is skipped.
+    Cadences are train_device's: reset_noise once per replay_frequency env steps; from learn_start on, beta annealed by
+    priority_weight_increase * S per round, one learn() per replay_frequency env steps (learn_owed), target update and on_eval
+    at `T % k < S`.  Returns the number of learn() calls made."""
+    S = len(emus)
+    if S != mem.streams or S != front.streams:
+        raise ValueError("train_host_vec: %d emulators, a front end of %d streams, a memory of %d" % (S, front.streams, mem.streams))
+    increase = (1 - args.priority_weight) / (T_max - args.learn_start)           # main.py:123
+    clip = float(getattr(args, "reward_clip", 0) or 0)
+    eval_every = int(getattr(args, "evaluation_interval", 0) or 0)
+    agent.train()
+    scr = front.screens
+    for s in range(S):
+        emus[s].reset(scr[s, 0])
+    states = front.reset_all()
+    flags, rewards, terminals = np.zeros(S, dtype=np.uint8), np.zeros(S, dtype=np.float32), np.zeros(S, dtype=bool)
+    learn_owed, learns = 0.0, 0
+    for T in range(1, T_max + 1, S):
+        if T % args.replay_frequency < S:
+            agent.reset_noise()                                                   # main.py:150-151
+        actions = agent.act_batch(states)                                         # main.py:153, one forward for all streams
+        scr = front.screens
+        for s in range(S):
+            f, r, done, life_lost = emus[s].step(int(actions[s]), scr[s, 0], scr[s, 1])    # main.py:154
+            if done or life_lost:                                                 # main.py:147-148, in the same round
+                emus[s].reset(scr[s, 0])
+                f = front.RESET if done else front.LIFE_RESET
+            flags[s], rewards[s], terminals[s] = f, r, done or life_lost
+        if clip > 0:
+            np.clip(rewards, -clip, clip, out=rewards)                            # main.py:155-156
+        next_states = front.step(flags)
+        mem.append_streams(states, actions, rewards, terminals)                   # main.py:157
         if T >= args.learn_start:
             mem.priority_weight = min(mem.priority_weight + increase * S, 1)      # main.py:161
             learn_owed += S / args.replay_frequency

@@ -3,7 +3,10 @@ for S in {1, 4, 16, 64}.  Per round: FramePreprocessor.observe on the S raw [210
 Agent.act_batch (one forward for all S), ReplayMemory.append_streams (one launch); and reset_noise + learn at the
 reference's replay ratio — one learn per `replay_frequency` (4) environment steps, i.e. S / 4 learns per round (one learn
 every 4 / S rounds below S = 4).  Prints one JSON line: env-steps/s of the whole loop and microseconds per piece, per S.
-Not the headline metric (bench.py is)."""
+Next to `observe_us` (observe + torch.cat: two launches) stand the figures of the one-launch front end,
+rainbow_amd.frames.FrameStackVec: `observe_stack_us` (step_device: the screens are on the device, as for observe_us) and
+`observe_stack_upload_us` (step: from the pinned slot, the upload of 2 * S raw screens included), measured in the same process.
+`--observe` measures only these three.  Not the headline metric (bench.py is)."""
 import json
 import os
 import sys
@@ -57,6 +60,39 @@ def fill(mem, lib, L, capacity, actions, seed):
     torch.cuda.synchronize(dev)
 
 
+def observe_figures(S, dev, screens=None):
+    """observe + torch.cat against FrameStackVec, interleaved blocks in one process, median of 7 blocks of 200 calls."""
+    from rainbow_amd.frames import FramePreprocessor, FrameStackVec
+    pre, front = FramePreprocessor(dev), FrameStackVec(S, dev)
+    if screens is None:
+        g = torch.Generator(device=dev).manual_seed(3)
+        screens = [torch.randint(0, 256, (S, 210, 160), dtype=torch.uint8, device=dev, generator=g) for _ in range(8)]
+    for slot in range(2):                     # both pinned slots hold screens
+        front.step(front.STEP, np.stack([screens[slot].cpu().numpy(), screens[slot + 1].cpu().numpy()], 1))
+    st = {"stacks": torch.zeros((S, 4, 84, 84), device=dev), "k": 0}
+
+    def observe():
+        st["k"] += 1
+        obs = pre.observe(screens[st["k"] & 7], screens[(st["k"] + 1) & 7])
+        st["stacks"] = torch.cat([st["stacks"][:, 1:], obs[:, None]], dim=1)      # env.py:70 deque, per stream
+
+    def stack_device():
+        st["k"] += 1
+        front.step_device(front.STEP, screens[st["k"] & 7], screens[(st["k"] + 1) & 7])
+
+    def stack_upload():
+        front.step(front.STEP)
+
+    legs = {"observe_us": observe, "observe_stack_us": stack_device, "observe_stack_upload_us": stack_upload}
+    for fn in legs.values():
+        timed(fn, 50, dev)
+    samples = {k: [] for k in legs}
+    for _ in range(7):
+        for k, fn in legs.items():
+            samples[k].append(timed(fn, 200, dev))
+    return {k: float(np.median(v)) for k, v in samples.items()}
+
+
 def run(S, capacity, rounds, dev):
     import __graft_entry__
     __graft_entry__.build()
@@ -104,7 +140,8 @@ def run(S, capacity, rounds, dev):
 
     for _ in range(20):
         round_()
-    out = {"observe_us": timed(observe, 200, dev), "act_batch_us": timed(act, 200, dev), "append_streams_us": timed(append, 200, dev)}
+    out = {"act_batch_us": timed(act, 200, dev), "append_streams_us": timed(append, 200, dev)}
+    out.update(observe_figures(S, dev, screens))
     for _ in range(20):
         learn()
     out["learn_us"] = timed(learn, 200, dev)
@@ -116,6 +153,11 @@ def run(S, capacity, rounds, dev):
 
 def main():
     dev = torch.device("cuda", 0)
+    if "--observe" in sys.argv[1:]:
+        import __graft_entry__
+        __graft_entry__.build()
+        print(json.dumps({"S%d" % S: {k: round(v, 2) for k, v in observe_figures(S, dev).items()} for S in (1, 4, 16, 64)}))
+        return
     capacity = int(os.environ.get("LOOP_CAPACITY", str(1 << 17)))      # a multiple of every S measured
     result = {"capacity": capacity}
     for S in (1, 4, 16, 64):
