@@ -351,6 +351,14 @@ int rb_learner_param_layout(const rb_learner_config_t* cfg, rb_tensor_desc_t* de
 /* Noise buffer layout: factorised vectors f(eps) (model.py:32-40), per layer
  * {name = fc_h_v.eps_in, fc_h_v.eps_out, ...}.                                      */
 int rb_learner_noise_layout(const rb_learner_config_t* cfg, rb_tensor_desc_t* descs, int32_t* n);
+/* Debug read-out (stateless: allocates nothing, touches no device): which kernel every launch of a learn step reaches for this
+ * config, with its grid, block and the scalars of the decision — one text line per launch ("tag kernel=... grid=XxYxZ block=N
+ * key=value ..."), then the conv and FC forward lines of a one-row f32 forward (the act / evaluate_q shape, tags "act_...").
+ * rb_opts: an RB_OPTS string (NULL = all defaults; the environment is NOT read); n_cu: compute units to plan for; flags:
+ * RB_LEARNER_* bits; world > 1: the replica exchange is set; with_sink: a priority sink is set.  The lines come from the very
+ * plan functions the launchers call (csrc/learner_plan.h).  RB_ERR_INVALID when `cap` bytes are too few.                     */
+int rb_debug_launch_plan(const rb_learner_config_t* cfg, const char* rb_opts, int32_t n_cu, int32_t flags, int32_t world,
+                         int32_t with_sink, char* out, int64_t cap);
 
 int rb_learner_create(rb_learner_t** out, const rb_learner_config_t* cfg, float* online_params_dev,
                       float* target_params_dev, float* grads_dev, float* online_noise_dev,

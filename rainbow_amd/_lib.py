@@ -69,6 +69,7 @@ SIGNATURES = {
     "rb_profile_read": (c_int, [C.POINTER(c_double), C.POINTER(c_int64)]),
     "rb_profile_overhead": (c_int, [c_void_p, c_int32, C.POINTER(c_double)]),
     "rb_debug_check_guards": (c_int, [C.POINTER(c_int64), C.POINTER(c_int64)]),
+    "rb_debug_launch_plan": (c_int, [C.POINTER(LearnerConfig), c_char_p, c_int32, c_int32, c_int32, c_int32, c_char_p, c_int64]),
     "rb_replay_create": (c_int, [C.POINTER(c_void_p), c_int64, c_int32, c_int32, c_double, c_double, c_uint64]),
     "rb_replay_create_streams": (c_int, [C.POINTER(c_void_p), c_int64, c_int32, c_int32, c_double, c_double, c_uint64, c_int32]),
     "rb_replay_streams": (c_int, [c_void_p, C.POINTER(c_int32)]),

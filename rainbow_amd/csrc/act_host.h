@@ -1,0 +1,196 @@
+// act_host.h — host side of Agent.act / evaluate_q: the one-launch act path (act_path.h) and the batched forward.
+// Included by learner.hip only, after fc_dispatch.h (forward, nl_h / nl_z) and head.h (k_head_act).
+#pragma once
+#include "learner_internal.h"
+
+// One state through the act path (act_path.h).  RB_ERR_STATE (without touching the error string) = geometry not
+// covered, the caller falls back to the training kernels.
+// Returns RB_OK (logits ready: the caller launches the head), 1 (the one-launch path ran the head as well and wrote
+// head_action_out / head_q_out), or an error.
+static int act_forward_single(rb_learner* l, const float* state_dev, const NetPtrs& on, int noisy, hipStream_t stream,
+                              int32_t* head_action_out, float* head_q_out) {
+  const Layout& L = l->L;
+  if (!l->caps.fast_fc || (L.F & 3) || (L.H & 3)) return RB_ERR_STATE;   // RB_OPTS generic=1 / 2 also lands here
+  int rg[3];
+  for (int layer = 0; layer < L.nconv; ++layer) {   // output rows per workgroup: <= 128 positions, patch fits the LDS
+    const ConvLayer& c = L.conv[layer];
+    int r = RB_ACT_MAXPOS / c.oh;
+    if (r > c.oh) r = c.oh;
+    while (r >= 1 && (int64_t)c.cin * ((r - 1) * c.s + c.ks) * c.ih > RB_ACT_LDS) --r;
+    if (r < 1 || c.K() > RB_ACT_KMAX) return RB_ERR_STATE;
+    rg[layer] = r;
+  }
+  ActFusedArgs f;
+  memset(&f, 0, sizeof(f));
+  const float* x = state_dev;
+  for (int layer = 0; layer < L.nconv; ++layer) {
+    const ConvLayer& c = L.conv[layer];
+    ActConvArgs& a = f.conv[layer];
+    a.x = x; a.w = on.conv_w[layer]; a.bias = on.conv_b[layer]; a.y = l->act[layer];
+    a.cin = c.cin; a.cout = c.cout; a.KS = c.ks; a.S = c.s; a.IH = c.ih; a.OH = c.oh; a.RG = rg[layer];
+    x = l->act[layer];
+  }
+  f.nconv = L.nconv;
+  ActFcArgs& h = f.h;
+  h.x = x; h.w = nl_h(on); h.K = L.F; h.n_rows = 2 * L.H; h.split_row = L.H; h.x_off1 = 0; h.ein_off1 = L.F;
+  h.out = l->h; h.relu = 1; h.mu_only = noisy ? 0 : 1;
+  ActFcArgs& z = f.z;
+  z.x = l->h; z.w = nl_z(on); z.K = L.H; z.n_rows = L.NZ; z.split_row = L.Z; z.x_off1 = L.H; z.ein_off1 = L.H;
+  z.out = l->logits; z.relu = 0; z.mu_only = noisy ? 0 : 1;
+  bool can_fuse = l->opt.act_fused != 0;
+  // (a captured launch would replay a stale launch number: under stream capture the per-layer launches below run instead)
+  if (can_fuse && rb_stream_capturing(stream)) can_fuse = false;
+  if (can_fuse) {
+    // ONE persistent launch (act_path.h k_act_fused): G workgroups, one per CU, all resident — the in-launch waits need that
+    f.Z = L.Z; f.A = L.A; f.logits = l->logits; f.support = l->support; f.action_out = head_action_out; f.q_out = head_q_out;
+    f.ctr = l->act_ctr; f.err = l->act_ctr + 6 * RB_FAN_SHARDS * RB_FAN_STRIDE;
+    int G = (l->n_cu < 256 ? l->n_cu : 256) / RB_FAN_SHARDS * RB_FAN_SHARDS;       // a multiple of the counter shards
+    if (G < RB_FAN_SHARDS) G = RB_FAN_SHARDS;
+#if defined(RB_HOST_INTERP)
+    // the host interpreter runs workgroups one after the other: one launch per phase (no in-launch dependency), same bodies
+    for (int ph = 0; ph < 6; ++ph) {
+      if (ph < 3 && ph >= L.nconv) continue;
+      f.phase_lo = ph; f.phase_hi = ph + 1; f.epoch = 0;
+      RB_LAUNCH(k_act_fused<0>, dim3((unsigned)G), dim3(256), stream, f);
+    }
+#else
+    f.phase_lo = 0; f.phase_hi = 6; f.epoch = l->act_epoch + 1;        // (counted below, once the launch is in the stream)
+    const int hq = (int)rb_div_up(L.F, 256);
+    if (hq <= 3) { RB_LAUNCH_T("act:k_act_fused", k_act_fused<3>, dim3((unsigned)G), dim3(256), stream, f); }
+    else if (hq <= 13) { RB_LAUNCH_T("act:k_act_fused", k_act_fused<13>, dim3((unsigned)G), dim3(256), stream, f); }
+    else { RB_LAUNCH_T("act:k_act_fused", k_act_fused<0>, dim3((unsigned)G), dim3(256), stream, f); }
+#endif
+    RB_LAUNCH_CHECK();
+#if !defined(RB_HOST_INTERP)
+    ++l->act_epoch;       // only a launch that went out advances the monotonic arrival targets (a refused one signalled nothing)
+#endif
+    return 1;                                              // the head ran inside the launch
+  }
+  for (int layer = 0; layer < L.nconv; ++layer) {
+    const ConvLayer& c = L.conv[layer];
+    RB_LAUNCH(k_act_conv, dim3((unsigned)c.cout, (unsigned)rb_div_up(c.oh, rg[layer])), dim3(256), stream, f.conv[layer]);
+    RB_LAUNCH_CHECK();
+  }
+  RB_LAUNCH(k_act_fc, dim3((unsigned)rb_div_up(h.n_rows, 4)), dim3(256), stream, h);
+  RB_LAUNCH_CHECK();
+  RB_LAUNCH(k_act_fc, dim3((unsigned)rb_div_up(z.n_rows, 4)), dim3(256), stream, z);
+  RB_LAUNCH_CHECK();
+  return RB_OK;
+}
+
+extern "C" {
+
+int rb_learner_act(rb_learner_t* l, const float* state_dev, int32_t noisy, int32_t* action_dev, float* q_dev,
+                   rb_stream_t stream) {
+  RB_REQUIRE(l && state_dev, "rb_learner_act: NULL argument");
+  RB_FLUSH_UPDATE(l, stream);
+  const Layout& L = l->L;
+  ImgSrc src;
+  memset(&src, 0, sizeof(src));
+  src.f32 = state_dev; src.B = 1;
+  const NetPtrs on = net_ptrs(L, l->p_online, noisy ? l->n_online : l->zero_noise);
+  int rc = act_forward_single(l, state_dev, on, noisy, (hipStream_t)stream, action_dev, q_dev);
+  if (rc == 1) return RB_OK;                                                          // one launch, head included
+  if (rc == RB_ERR_STATE) rc = forward(l, 1, 0, src, on, on, (hipStream_t)stream);   // geometry outside the act path
+  if (rc != RB_OK) return rc;
+  RB_LAUNCH(k_head_act, dim3(1), dim3(256), stream, L.Z, L.A, (const float*)l->logits, 0, (const float*)l->support,
+            action_dev, q_dev);
+  RB_LAUNCH_CHECK();
+  return RB_OK;
+}
+
+// rb_learner_act + waiting for its result on the host, in one call (include/rainbow_hip.h): the action word is preset, the launch
+// goes out, and the pinned word is polled HERE — a compiled loop sees the head's store within tens of nanoseconds, a Python loop
+// over a numpy scalar within a microsecond or two, and the caller saves the interpreter's share of a 43 us act().
+int rb_learner_act_wait(rb_learner_t* l, const float* state_dev, int32_t noisy, int32_t* action_pinned, float* q_pinned,
+                        int32_t* action_out, float* q_out, rb_stream_t stream) {
+  RB_REQUIRE(l && state_dev && action_pinned && q_pinned, "rb_learner_act_wait: NULL argument");
+  constexpr int32_t PENDING = -7;
+  int attempts = 0;
+  for (;;) {
+    *(volatile int32_t*)action_pinned = PENDING;
+    const int rc = rb_learner_act(l, state_dev, noisy, action_pinned, q_pinned, stream);
+    if (rc != RB_OK) return rc;
+#if !defined(RB_HOST_INTERP)
+    bool seen = false;
+    for (long spin = 0; spin < 4000000L; ++spin) {           // ~10 ms of polling, then the stream is synchronised instead
+      if (*(volatile int32_t*)action_pinned != PENDING) { seen = true; break; }
+    }
+    if (!seen) RB_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+#endif
+    int32_t a = *(volatile int32_t*)action_pinned;
+#if !defined(RB_HOST_INTERP)
+    if (a < 0) {                                             // an error code (or a torn view): the final word after a synchronise
+      RB_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+      a = *(volatile int32_t*)action_pinned;
+    }
+#endif
+    if (a >= 0) {
+      if (action_out) *action_out = a;
+      if (q_out) *q_out = *(volatile float*)q_pinned;        // (the head stores q, fences, then the action)
+      return RB_OK;
+    }
+    // the one-launch path reported an expired in-launch wait of THAT launch (its workgroups were not co-resident); the failure is
+    // tagged with the launch number, so the next launch starts clean: once more, then give up
+    if (++attempts >= 2) {
+      rb_set_error("rb_learner_act_wait: the one-launch act path reported an expired in-launch wait twice (action %d); "
+                   "RB_OPTS=act_fused=0 selects the per-layer launches", (int)a);
+      return RB_ERR_STATE;
+    }
+  }
+}
+
+}  // extern "C"
+
+// The forward buffers are sized for the learn step's 3B images; batched evaluation (test.py:38-39 over a 500-state
+// validation memory) may ask for more rows: grow them (synchronising; happens once per size).
+static int ensure_rows(rb_learner* l, int rows) {
+  if (rows <= l->rows_cap) return RB_OK;
+  const Layout& L = l->L;
+  RB_HIP_TRY(hipDeviceSynchronize());
+  auto regrow = [&](float** p, int64_t count) -> int {
+    if (*p) rb_dev_free(*p);
+    *p = nullptr;
+    hipError_t e = rb_dev_malloc((void**)p, (size_t)count * 4);
+    if (e != hipSuccess) { rb_set_error("rb_learner_act_batch: hipMalloc(%lld B) failed: %s", (long long)count * 4, hipGetErrorString(e)); return RB_ERR_OOM; }
+    return RB_OK;
+  };
+  int rc;
+  for (int i = 0; i < L.nconv; ++i)
+    if ((rc = regrow(&l->act[i], (int64_t)rows * L.conv[i].cout * L.conv[i].P())) != RB_OK) return rc;
+  if ((rc = regrow(&l->hpart, (int64_t)l->caps.hs * rows * 2 * L.H)) != RB_OK) return rc;
+  if ((rc = regrow(&l->h, (int64_t)rows * 2 * L.H)) != RB_OK) return rc;
+  if ((rc = regrow(&l->feat_b, (int64_t)rows * (L.F + 16))) != RB_OK) return rc;
+  if ((rc = regrow(&l->h_b, (int64_t)rows * (2 * L.H + 16))) != RB_OK) return rc;
+  if ((rc = regrow(&l->logits, (int64_t)rows * L.NZ)) != RB_OK) return rc;
+  RB_HIP_TRY(hipMemset(l->hpart, 0, (size_t)l->caps.hs * rows * 2 * L.H * 4));
+  l->rows_cap = rows;
+  return RB_OK;
+}
+
+extern "C" {
+
+int rb_learner_act_batch(rb_learner_t* l, const float* states_dev, int32_t n, int32_t noisy, int32_t* actions_dev,
+                         float* q_dev, rb_stream_t stream) {
+  RB_REQUIRE(l && states_dev, "rb_learner_act_batch: NULL argument");
+  RB_FLUSH_UPDATE(l, stream);
+  const Layout& L = l->L;
+  RB_REQUIRE(n >= 1 && n <= 4096, "rb_learner_act_batch: n must be in [1, 4096]");
+  {
+    int rc0 = ensure_rows(l, n);
+    if (rc0 != RB_OK) return rc0;
+  }
+  if (n == 1) return rb_learner_act(l, states_dev, noisy, actions_dev, q_dev, stream);
+  ImgSrc src;
+  memset(&src, 0, sizeof(src));
+  src.f32 = states_dev; src.B = n;
+  const NetPtrs on = net_ptrs(L, l->p_online, noisy ? l->n_online : l->zero_noise);
+  int rc = forward(l, n, 0, src, on, on, (hipStream_t)stream);     // the training kernels: n images share every weight read
+  if (rc != RB_OK) return rc;
+  RB_LAUNCH(k_head_act, dim3((unsigned)n), dim3(256), stream, L.Z, L.A, (const float*)l->logits, 0, (const float*)l->support,
+            actions_dev, q_dev);
+  RB_LAUNCH_CHECK();
+  return RB_OK;
+}
+
+}  // extern "C"

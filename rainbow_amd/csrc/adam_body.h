@@ -1,5 +1,5 @@
 // adam_body.h — clip_grad_norm_ + Adam (agent.py:97-98) as a device body that a foreign launch can host.
-// k_clip_adam (learner.hip) runs it as a launch of its own; k_sample (replay.hip) can carry it as extra workgroups: the
+// k_clip_adam (adam_kernels.h) runs it as a launch of its own; k_sample (replay.hip) can carry it as extra workgroups: the
 // optimiser pass of learn call k has no data dependency on the sampler of call k + 1 (it reads the gradient, its norm
 // partials and the moments; the sampler reads the sum-tree, whose write-back happened in call k's backward), so when two
 // learn calls follow each other the 6.4 M-parameter streaming pass runs beside the sampler's serial, latency-bound

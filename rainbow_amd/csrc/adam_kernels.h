@@ -1,0 +1,195 @@
+// adam_kernels.h — the optimiser pass as launches of its own (adam_body.h has the element bodies and the hosted form).
+// Included by learner.hip only (non-template kernels).
+#pragma once
+#include "learner_internal.h"
+
+// (ClipAdamArgs, rb_adam_elem / rb_adam_quad and the hosted form of the pass: adam_body.h)
+// Tile part of the fused optimiser pass (batch <= 32).  The hidden layer's weight gradient is a rank-B product,
+// g_mu = dY^T X  (dY [B][2H], X [B][F], both L2-resident: 0.5 MB), g_sigma = g_mu * (eps_out x eps_in).  Writing it in the
+// backward and reading it back here costs 2 x 25.7 MB of HBM traffic per step; instead a wave recomputes its 16 x 64
+// tile with 32 MFMAs (same operand order as rb_nl_dw_body_pipe, so the bits equal those of the backward's norm-only
+// pass) while its p / m / v loads are in flight, and applies clip + Adam to mu and sigma right there: 6 array passes
+// over the 6.4 M weights instead of 9.
+struct FusedDwAdamArgs {
+  NlDwArgs dw;                 // operands of the weight gradient (g_* unused)
+  int64_t mu_off, sigma_off;   // offsets of the [2H][F] mu / sigma arrays inside p, m, v (and g)
+  int dw_x, n_tile_blocks;     // 256-column block columns; 256-thread tile blocks = dw_x * (2H / 16)
+  int write_grads;             // tests: also store the (unclipped... as clip_grad_norm_ leaves it: clipped) gradient tile
+};
+// Each tile is taken by TWO workgroup slots: slot 0 updates mu, slot 1 sigma (both recompute the same 32 MFMAs — 0.4 GFLOP
+// extra per step against 24 fewer live registers per lane: 4 waves per SIMD instead of 2, no spills; the single-slot
+// version measured 36.5 us per launch against 35.0 for the plain streaming pass, i.e. slower despite 13 % fewer bytes).
+template <bool WT>
+__device__ __forceinline__ void rb_fused_dw_adam_tile(const ClipAdamArgs& a, const FusedDwAdamArgs& f, int b2, float coef) {
+  const NlDwArgs& d = f.dw;
+  const int lane = rb_lane(), wave = rb_wave();
+  const int which = b2 & 1, b = b2 >> 1;                 // 0: mu, 1: sigma
+  const int bx = b % f.dw_x, by = b / f.dw_x;
+  const int kt = bx * 256 + wave * 64;
+  if (kt >= d.K) return;                                  // wave-uniform
+  const int g = (d.n_prob > 1 && by >= d.prob[1].tile_begin) ? 1 : 0;
+  const NlDwProblem pr = d.prob[g];
+  const int row0 = pr.row_begin + (by - pr.tile_begin) * 16;
+  const int row_end = pr.row_begin + pr.row_cnt;
+  const int c = lane & 15, q = lane >> 4;
+  int col4 = kt + 4 * c;
+  const bool cv = col4 < d.K;
+  if (!cv) col4 = d.K - 4;
+  int arow = row0 + c;
+  const bool av_ok = arow < row_end;
+  if (!av_ok) arow = row_end - 1;
+  const int64_t arr = which ? f.sigma_off : f.mu_off;
+  // operands of the gradient tile first (they gate the MFMAs), then the 12 parameter / moment quads (they gate the update)
+  float avs[8];
+  float4 xs[8];
+#pragma unroll
+  for (int st = 0; st < 8; ++st) {
+    const int m = 4 * st + q;
+    const bool mv = m < d.M;
+    const int mcl = mv ? m : d.M - 1;
+    avs[st] = (mv && av_ok) ? d.dy[(int64_t)mcl * d.ldy + arow] : 0.0f;
+    xs[st] = rb_ld4(d.x + (int64_t)mcl * d.ldx + pr.x_off + col4);
+    if (!mv) { xs[st].x = 0.0f; xs[st].y = 0.0f; xs[st].z = 0.0f; xs[st].w = 0.0f; }
+  }
+  const float4 e4 = rb_ld4(d.ein + pr.ein_off + col4);
+  float eo4[4];
+  int64_t off[4];
+  float4 P[4], M[4], V[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    int n = row0 + 4 * q + e;
+    if (n > row_end - 1) n = row_end - 1;                 // clamped rows are loaded (legal) and never stored
+    eo4[e] = d.eout[n];
+    off[e] = arr + (int64_t)n * d.K + col4;
+    P[e] = rb_ld4(a.p + off[e]); M[e] = rb_ld4(a.m + off[e]); V[e] = rb_ld4(a.v + off[e]);
+  }
+  rb_f32x4 acc[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { acc[0][e] = 0.0f; acc[1][e] = 0.0f; acc[2][e] = 0.0f; acc[3][e] = 0.0f; }
+#pragma unroll
+  for (int st = 0; st < 8; ++st) {
+    if (4 * st < d.M) {                                   // uniform
+      acc[0] = rb_mfma16(avs[st], xs[st].x, acc[0]);
+      acc[1] = rb_mfma16(avs[st], xs[st].y, acc[1]);
+      acc[2] = rb_mfma16(avs[st], xs[st].z, acc[2]);
+      acc[3] = rb_mfma16(avs[st], xs[st].w, acc[3]);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int n = row0 + 4 * q + e;
+    if (n < row_end && cv) {
+      float4 gr;
+      gr.x = acc[0][e]; gr.y = acc[1][e]; gr.z = acc[2][e]; gr.w = acc[3][e];
+      if (which) {                                        // block-uniform: g_sigma = g_mu * (eps_out * eps_in), model.py:39,44
+        const float eo = eo4[e];
+        gr.x = gr.x * (eo * e4.x); gr.y = gr.y * (eo * e4.y); gr.z = gr.z * (eo * e4.z); gr.w = gr.w * (eo * e4.w);
+      }
+      rb_adam_quad(P[e], gr, M[e], V[e], coef, a);
+      if (WT) {
+        const unsigned o = (unsigned)(4 * off[e]);
+        rb_st4_wt(a.p, o, P[e]); rb_st4_wt(a.m, o, M[e]); rb_st4_wt(a.v, o, V[e]);
+      } else {
+        rb_st4(a.p + off[e], P[e]); rb_st4(a.m + off[e], M[e]); rb_st4(a.v + off[e], V[e]);
+      }
+      if (f.write_grads) rb_st4(a.g + off[e], gr);         // as clip_grad_norm_ leaves .grad: scaled when the clip bites
+    }
+  }
+}
+#define RB_ADAM_MINWAVES 1
+template <int RB_ADAM_UNROLL, bool WT, bool FUSED>   // float4 quadruples (p, g, m, v) in flight per thread; WT: write-through stores
+__global__ __launch_bounds__(256, RB_ADAM_MINWAVES) void k_clip_adam(ClipAdamArgs a, FusedDwAdamArgs f) {
+  __shared__ float s_red[18];      // [0, 16) rb_block_sum's wave slots; [16], [17] the bias-correction scalars (slots of their own:
+                                   // thread 0 writes them while other waves may still be reading the wave slots of the sum —
+                                   // the host interpreter's schedule turned that into a wrong clip coefficient for every thread
+                                   // but thread 0 whenever the clip bit and the step number came from the device counter)
+  const bool tile_block = FUSED && (int)blockIdx.x < f.n_tile_blocks;
+  const int64_t n4 = (a.n >> 2) - (FUSED ? a.skip_len4 : 0);
+  const int eb = FUSED ? (int)blockIdx.x - f.n_tile_blocks : (int)blockIdx.x;
+  const int64_t base = (int64_t)eb * (256 * RB_ADAM_UNROLL) + threadIdx.x;
+  float4 P[RB_ADAM_UNROLL], G[RB_ADAM_UNROLL], M[RB_ADAM_UNROLL], V[RB_ADAM_UNROLL];
+  int64_t idx[RB_ADAM_UNROLL];
+  if (!tile_block) {
+#pragma unroll
+    for (int u = 0; u < RB_ADAM_UNROLL; ++u) {
+      int64_t i = base + u * 256;
+      if (i >= n4) i = n4 > 0 ? n4 - 1 : 0;          // clamped load (always legal), masked store
+      if (FUSED && i >= a.skip_lo4) i += a.skip_len4;
+      idx[u] = i;
+      P[u] = rb_ld4(a.p + 4 * i); G[u] = rb_ld4(a.g + 4 * i); M[u] = rb_ld4(a.m + 4 * i); V[u] = rb_ld4(a.v + 4 * i);
+    }
+  }
+  if (a.batch_status && *a.batch_status != 0) {                     // block-uniform (every block reads the same word)
+    if (blockIdx.x == 0 && threadIdx.x == 0 && a.norm_out) *a.norm_out = 0.0f;
+    return;
+  }
+  float acc = 0.0f;
+  for (int i = (int)threadIdx.x; i < a.nparts; i += 256) acc += a.part[i];
+  acc = rb_block_sum(acc, s_red);
+  const float total = sqrtf(acc);
+  float coef = a.max_norm / (total + 1e-6f);
+  if (coef > 1.0f) coef = 1.0f;                                    // clamp(max=1.0)
+  if (blockIdx.x == 0 && threadIdx.x == 0 && a.norm_out) *a.norm_out = total;
+  if (a.step_dev) {                                                // block-uniform
+    if (threadIdx.x == 0) {
+      const double t = (double)*a.step_dev;
+      const double bc1 = 1.0 - pow(a.beta1, t), bc2 = 1.0 - pow(a.beta2, t);
+      s_red[16] = (float)(-(a.lr / bc1));
+      s_red[17] = (float)sqrt(bc2);
+    }
+    __syncthreads();
+    a.neg_step_size = s_red[16];
+    a.bc2_sqrt = s_red[17];
+  }
+  if (tile_block) {
+    rb_fused_dw_adam_tile<WT>(a, f, (int)blockIdx.x, coef);
+    return;
+  }
+#pragma unroll
+  for (int u = 0; u < RB_ADAM_UNROLL; ++u) {
+    if (base + u * 256 >= n4) continue;
+    const int64_t i = idx[u];
+    rb_adam_quad(P[u], G[u], M[u], V[u], coef, a);
+    if (WT) {
+      const unsigned off = (unsigned)(16 * i);
+      rb_st4_wt(a.p, off, P[u]); rb_st4_wt(a.m, off, M[u]); rb_st4_wt(a.v, off, V[u]);
+    } else {
+      rb_st4(a.p + 4 * i, P[u]); rb_st4(a.m + 4 * i, M[u]); rb_st4(a.v + 4 * i, V[u]);
+    }
+    if (coef < 1.0f) rb_st4(a.g + 4 * i, G[u]);
+  }
+  // tail (n % 4 elements): last block's first threads
+  if (blockIdx.x == gridDim.x - 1) {
+    const int64_t t = ((a.n >> 2) << 2) + threadIdx.x;
+    if (t < a.n) {
+      float p = a.p[t], g = a.g[t], m = a.m[t], v = a.v[t];
+      rb_adam_elem(p, g, m, v, coef, a);
+      a.p[t] = p; a.m[t] = m; a.v[t] = v;
+      if (coef < 1.0f) a.g[t] = g;
+    }
+  }
+}
+
+extern "C" {      // (C linkage: the names a kernel trace has always shown for these two)
+
+// g_sigma = g_mu * (eps_out[n] * eps_in[k]) for the hidden layer, from the noise snapshot of the learn call that produced g_mu:
+// what RB_LEARNER_IMPLICIT_SIGMA's backward left out, for every consumer of the flat gradient other than the hosted pass
+__global__ __launch_bounds__(256) void k_materialize_sigma(float* g, int64_t mu4, int64_t len4, int f4, int split_row,
+                                                            const float* eout, const float* ein, const int32_t* clipped) {
+  if (*clipped != 0) return;          // the optimiser pass has stored the scaled gradients already (block-uniform)
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < len4; j += (int64_t)gridDim.x * blockDim.x) {
+    const int row = (int)(j / f4), cq = (int)(j - (int64_t)row * f4);
+    const float eo = eout[row];
+    const float4 e = rb_ld4(ein + 4 * (int64_t)(cq + (row >= split_row ? f4 : 0)));
+    const float4 gm = rb_ld4(g + 4 * (mu4 + j));
+    float4 gs;
+    gs.x = gm.x * (eo * e.x); gs.y = gm.y * (eo * e.y); gs.z = gm.z * (eo * e.z); gs.w = gm.w * (eo * e.w);
+    rb_st4(g + 4 * (mu4 + len4 + j), gs);
+  }
+}
+
+__global__ void k_store_adam_args(ClipAdamArgs a, ClipAdamArgs* dst) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *dst = a;
+}
+
+}  // extern "C"

@@ -1851,7 +1851,7 @@ struct ConvDwAllArgs {
   int nblocks[3];          // workgroups of each layer
   int cotiles[3];
   int batch;
-  int ipb[3];              // images summed per workgroup, per layer (the layers' workgroups cost differently: learner.hip conv_dw_all)
+  int ipb[3];              // images summed per workgroup, per layer (the layers' workgroups cost differently: learner_plan.h plan_conv_dw_all)
   int img_fast;            // decode with the image group as the FASTEST index (see k_conv_fwd_lds): needs block ranges and group
                            // counts that are multiples of 8
 };

@@ -1,4 +1,4 @@
-// obs_stack.h — the observation front end of S host emulators on the device (included by replay.hip; the rules are in
+// obs_stack.h — the observation front end of S host emulators on the device (included by frames.hip; the rules are in
 // include/rainbow_hip.h).
 //
 // env.py's wrapper around the emulator, for all S streams in ONE launch per round: the 84 x 84 resize of the raw u8 screens
@@ -10,8 +10,10 @@
 #pragma once
 #include "rb_common.h"
 
+#include <string.h>
+
 // ---- OpenCV's 8-bit fixed-point INTER_LINEAR (11-bit coefficients; oracle/frame_oracle.py has the algebra and says why this
-// row is parity-UNPINNED: cv2 is absent here).  Shared by k_frame_preprocess (replay.hip) and k_obs_stack.
+// row is parity-UNPINNED: cv2 is absent here).  Shared by k_frame_preprocess (frames.hip) and k_obs_stack.
 __device__ __forceinline__ void rb_resize_tap(int d, int dst, int src, bool clamp_f, int* s_out, int* c0, int* c1) {
   const double scale = (double)src / (double)dst;
   float f = (float)__dsub_rn(__dmul_rn((double)d + 0.5, scale), 0.5);          // float((d + 0.5) * scale - 0.5)

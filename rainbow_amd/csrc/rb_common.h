@@ -43,6 +43,10 @@ void rb_dev_free(void* p);
 
 static inline int64_t rb_div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// most interleaved environment streams of a vectorised replay, frame-stack front end or device environment (their per-stream
+// scalars travel by value in a kernel's argument block)
+#define RB_MAX_STREAMS 64
+
 // Is `stream` being captured into a hipGraph right now?  (A query error counts as "yes": the callers take the conservative path.)
 // Whatever a captured launch bakes in is replayed verbatim: nothing in it may depend on work outside the graph or on a launch number.
 static inline bool rb_stream_capturing(void* stream) {

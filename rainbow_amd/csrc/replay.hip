@@ -158,7 +158,6 @@ __global__ __launch_bounds__(256) void k_append_one(ReplayView v, const float* l
 // operands, no staging) or from device arrays (AppendRoundDev: rb_replay_append_streams_dev, a round whose operands never
 // left the device); the kernel body is the same for both.  With device operands the timestep vector is in/out: the lane that
 // stored stream t's timestep writes back the stream's next one (memory.py:108), so the caller keeps no host copy of it.
-#define RB_MAX_STREAMS 64
 struct AppendRound {
   int32_t timestep[RB_MAX_STREAMS];
   int32_t action[RB_MAX_STREAMS];
@@ -241,31 +240,6 @@ __global__ __launch_bounds__(256) void k_append_streams(ReplayView v, const floa
     if (next == 0) v.hdr->full = 1;                   // memory.py:60
     v.hdr->total = s_val[cur][0];                     // the root
   }
-}
-
-// ---------------------------------------------------------------- frame pipeline --
-// env.py:27-29 (cv2.resize(gray [H][W] u8, (84, 84), INTER_LINEAR) -> f32 / 255) and env.py:57-69 (element-wise max over the
-// last two frames of the action repeat) on the device: raw emulator screens in, the observation the actor and
-// ReplayMemory.append consume out — no host-side resize, no 28 KB H2D float frame per environment step.
-// The resize is OpenCV's 8-bit fixed-point INTER_LINEAR (11-bit coefficients; oracle/frame_oracle.py has the algebra and
-// says why this row is parity-UNPINNED: cv2 is absent here).  One thread per output pixel; the taps of a pixel are four
-// bytes per frame, the coefficients two float operations — nothing worth staging.
-#include "obs_stack.h"   // rb_resize_tap / rb_resize_pixel, and the S-stream frame-stack front end (rb_obs_stack_step)
-__global__ __launch_bounds__(256) void k_frame_preprocess(const uint8_t* a, const uint8_t* b, int H, int W, int n_pairs,
-                                                           int64_t pair_stride, float* out) {
-  const int pair = (int)blockIdx.y;
-  const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (p >= 84 * 84 || pair >= n_pairs) return;
-  const int dy = p / 84, dx = p - dy * 84;
-  int sx, a0, a1, sy, b0, b1;
-  rb_resize_tap(dx, 84, W, true, &sx, &a0, &a1);
-  rb_resize_tap(dy, 84, H, false, &sy, &b0, &b1);
-  int v = rb_resize_pixel(a + pair * pair_stride, H, W, sx, a0, a1, sy, b0, b1);
-  if (b) {
-    const int w = rb_resize_pixel(b + pair * pair_stride, H, W, sx, a0, a1, sy, b0, b1);
-    v = w > v ? w : v;                               // max of the two states == state of the max (x / 255 is monotone)
-  }
-  out[(int64_t)pair * 84 * 84 + p] = __fdiv_rn((float)(v & 0xFF), 255.0f);    // torch .div_(255)
 }
 
 // Bulk append: frames + columns + leaves (any grid), then ancestor rebuild kernels.
@@ -582,7 +556,7 @@ __device__ long long g_stamp[32];
 // allocation, i.e. 2 waves per SIMD under the 256-thread variant's 205 VGPRs (needs AU = 8 to keep enough bytes in flight:
 // 42 us per hosted launch against 46 with AU = 4) and 4 under the 1024-thread variant's 127 (AU = 4)
 #define RB_HOST_AU_WIDE 4      // quadruples per hosted thread under the 1024-thread variant (5 spills under its 128-register cap)
-// (learner.hip sizes the pending pass for 4 quadruples per plain thread and 2 (mu, sigma) pairs per pair thread — pair_blk0 and
+// (optimizer_host.h clip_adam_impl sizes the pending pass for 4 quadruples per plain thread and 2 (mu, sigma) pairs per pair thread — pair_blk0 and
 // the pair grid in clip_adam_impl; the hosting launch rescales the block count by this constant: any other value would split
 // plain and pair workgroups differently from what the pass expects)
 template <int MAXT>
@@ -982,11 +956,6 @@ __global__ __launch_bounds__(256) void k_states_at(ReplayView v, const int64_t* 
     for (int p = (int)threadIdx.x; p < RB_FRAME_BYTES; p += (int)blockDim.x)
       dst[p] = blank ? 0.0f : __fdiv_rn((float)src[p], 255.0f);
   }
-}
-
-__global__ __launch_bounds__(256) void k_u8_to_unit(const uint8_t* src, float* dst, int64_t n) {
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
-    dst[t] = __fdiv_rn((float)src[t], 255.0f);  // memory.py:137 .div_(255)
 }
 
 // ================================================================ host entry points
@@ -1576,33 +1545,9 @@ int rb_replay_states_at(rb_replay_t* r, const int64_t* data_index_dev, int32_t n
   return RB_OK;
 }
 
-int rb_frame_preprocess(const uint8_t* frame_a_dev, const uint8_t* frame_b_dev, int32_t height, int32_t width, int32_t n,
-                        float* out_dev, rb_stream_t stream) {
-  RB_REQUIRE(frame_a_dev && out_dev, "rb_frame_preprocess: NULL argument");
-  RB_REQUIRE(height >= 2 && width >= 2 && height <= 4096 && width <= 4096, "rb_frame_preprocess: frame size must be in [2, 4096]^2");
-  RB_REQUIRE(n >= 0, "rb_frame_preprocess: n must be >= 0");
-  if (n == 0) return RB_OK;
-  RB_LAUNCH(k_frame_preprocess, dim3((unsigned)rb_div_up(84 * 84, 256), (unsigned)n), dim3(256), stream, frame_a_dev, frame_b_dev,
-            height, width, n, (int64_t)height * width, out_dev);
-  RB_LAUNCH_CHECK();
-  return RB_OK;
-}
-
-int rb_u8_to_unit_f32(const uint8_t* src_dev, float* dst_dev, int64_t n, rb_stream_t stream) {
-  RB_REQUIRE(src_dev && dst_dev && n >= 0, "rb_u8_to_unit_f32: bad argument");
-  if (n == 0) return RB_OK;
-  int64_t g = rb_div_up(n, 256);
-  if (g > 4096) g = 4096;
-  RB_LAUNCH(k_u8_to_unit, dim3((unsigned)g), dim3(256), stream, src_dev, dst_dev, n);
-  RB_LAUNCH_CHECK();
-  return RB_OK;
-}
-
 }  // extern "C"
 
-#include "vec_env.h"   // device-resident environments (rb_catch_*)
-
-// (C++ linkage: called by learner.hip flush_update, not part of the C ABI)
+// (C++ linkage: called by optimizer_host.h flush_update, not part of the C ABI)
 int rb_launch_adam_pending(const ClipAdamArgs* args_dev, int blocks, void* stream) {
   RB_LAUNCH_T("clip_adam:k_adam_pending", k_adam_pending, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, args_dev);
   RB_LAUNCH_CHECK();

@@ -1,4 +1,4 @@
-// vec_env.h — environments that live on the device (included by replay.hip; the rules of the game are in include/rainbow_hip.h).
+// vec_env.h — environments that live on the device (the whole of vec_env.hip; the rules of the game are in include/rainbow_hip.h).
 //
 // Catch on the 84 x 84 screen, S independent streams, one 256-thread workgroup per stream.  A step is a tiny, latency-bound
 // launch: 16 bytes of game state per stream, then history frames of 28 KB written with 16-byte lanes (the shifted stack is
@@ -6,6 +6,8 @@
 // nonterminals and the next stacks go to device arrays, the episode totals accumulate per stream in the state block.
 #pragma once
 #include "rb_common.h"
+
+#include <string.h>
 
 #define RB_CATCH_GRID 12
 #define RB_CATCH_CELL 7

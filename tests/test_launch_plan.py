@@ -1,0 +1,268 @@
+"""Which kernel a shape reaches, pinned: rb_debug_launch_plan prints the plans of csrc/learner_plan.h — the very functions the
+launchers call — and this file holds them against the project's own record: the kernel tables of DESIGN.md sections 3 and 8, the
+kernel names of profiles/round6_final_cfg{2,3,4}_kernel_stats.csv, and the workgroup counts DESIGN.md and the code comments state
+(480 / 224 / 249 workgroups, 7 / 7 / 8 images, 48 tiles x split-K 5, 13 waves, ...).  No device: the entry touches none, and it
+is called here through the host-interpreter build with 256 compute units, the MI355X's count.  The GPU parity tests cannot see a
+step that silently falls back to a slower kernel; this can."""
+import csv
+import ctypes as C
+import os
+import re
+
+import pytest
+
+from hipemu import loader
+from rainbow_amd import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEFAULT_FLAGS = _lib.LEARNER_DEFER_UPDATE | _lib.LEARNER_IMPLICIT_SIGMA      # what Agent sets on one device (agent.py)
+
+
+@pytest.fixture(scope="module")
+def emu():
+    return loader.load()
+
+
+def plan(lib, batch=32, atoms=51, actions=6, history=4, hidden=512, architecture=0, opts=None, flags=DEFAULT_FLAGS, world=1,
+         sink=1, cap=1 << 14):
+    """-> {tag: {"kernel": str, "grid": (x, y, z), "block": int, key: int, ...}} in launch order."""
+    cfg = _lib.LearnerConfig(batch=batch, atoms=atoms, actions=actions, history=history, hidden=hidden, architecture=architecture,
+                             multi_step=3, v_min=-10.0, v_max=10.0, discount=0.99)
+    buf = C.create_string_buffer(cap)
+    rc = lib.rb_debug_launch_plan(C.byref(cfg), opts.encode() if opts else None, 256, flags, world, sink, buf, cap)
+    assert rc == 0, lib.rb_last_error()
+    out = {}
+    for line in buf.value.decode().splitlines():
+        tag, *fields = line.split(" ")
+        row = {}
+        for f in fields:
+            k, v = f.split("=", 1)
+            if k == "kernel":
+                row[k] = v
+            elif k == "grid":
+                row[k] = tuple(int(x) for x in v.split("x"))
+            elif "/" in v:
+                row[k] = tuple(int(x) for x in v.split("/"))
+            elif "x" in v:
+                row[k] = tuple(int(x) for x in v.split("x"))
+            else:
+                row[k] = int(v)
+        assert tag not in out, tag
+        out[tag] = row
+    return out
+
+
+def wgs(row):
+    g = row["grid"]
+    return g[0] * g[1] * g[2]
+
+
+def base(kernel):
+    return kernel.split("<")[0]
+
+
+CANONICAL = dict()                                                   # config 2: B 32, A 6
+B256 = dict(batch=256, actions=4)                                    # config 3
+DATA_EFF = dict(architecture=1, hidden=256)                          # config 4
+
+
+def recorded_kernels(cfg):
+    """Base names of the library's kernels in the recorded rocprofv3 statistics of a config."""
+    names = set()
+    with open(os.path.join(ROOT, "profiles", "round6_final_cfg%d_kernel_stats.csv" % cfg)) as f:
+        for row in csv.DictReader(f):
+            m = re.match(r"(?:void )?(k_[a-z0-9_]+)", row["Name"])
+            if m:
+                names.add(m.group(1))
+    return names
+
+
+# ---------------------------------------------------------------------------------------- the three benchmark configs
+def test_canonical_batch_32_reaches_the_kernels_of_design_3_1(emu):
+    p = plan(emu, **CANONICAL)
+    for i in (1, 2, 3):
+        assert base(p["conv%d_fwd" % i]["kernel"]) == "k_conv_fwd_t16"
+        assert p["conv%d_fwd" % i]["img_fast"] == 1
+    assert wgs(p["conv1_fwd"]) == 480 and p["conv1_fwd"]["grid"][0] == 96          # 5 x 96, the image index fastest
+    assert p["fc_h_fwd"]["kernel"] == "k_nl_fwd3<2>" and p["fc_z_fwd"]["kernel"] == "k_nl_fwd3<2>"
+    assert p["head"]["kernel"] == "k_head<1>" and p["head"]["grid"] == (32 + 96, 1, 1) and p["head"]["waves"] == 13
+    assert p["head"]["samples"] == 32 and p["head"]["tenants"] == 96 and p["head"]["block"] == 64 * 13
+    assert p["fc_z_bwd"]["kernel"] == "k_nl_bwd<true>"
+    assert p["fc_h_bwd"]["kernel"] == "k_nl_bwd<false>" and p["fc_h_bwd"]["writeback"] == 1
+    assert p["conv3_dx"]["kernel"] == "k_conv_dx_lds<GeomC3,MULTI=false>"
+    assert p["conv2_dx"]["kernel"] == "k_conv_dx_lds<GeomC2,MULTI=false>"
+    assert p["conv_dw_all"]["kernel"] == "k_conv_dw_all<3>" and p["conv_dw_all"]["nblocks"] == (96, 64, 64)
+    assert wgs(p["conv_dw_all"]) == 224
+    assert p["fc_h_bwd"]["implicit_sigma"] == 1 and p["fc_h_bwd"]["fuse_norm"] == 1 and p["fc_h_bwd"]["defer_dw"] == 0
+    assert "dfeat_finish" not in p and "pack_factors" not in p
+    # without a sink there is no write-back block
+    q = plan(emu, sink=0, **CANONICAL)
+    assert q["fc_h_bwd"]["writeback"] == 0 and wgs(q["fc_h_bwd"]) == wgs(p["fc_h_bwd"]) - 1
+    # without the flag the sigma gradient is stored
+    assert plan(emu, flags=0, **CANONICAL)["fc_h_bwd"]["implicit_sigma"] == 0
+
+
+def test_batch_256_reaches_the_kernels_of_design_3_2(emu):
+    p = plan(emu, **B256)
+    assert p["conv1_fwd"]["kernel"] == "k_conv_fwd_full<GeomC1>" and p["conv1_fwd"]["ipb"] == 3 and wgs(p["conv1_fwd"]) == 256
+    for i in (2, 3):
+        r = p["conv%d_fwd" % i]
+        assert base(r["kernel"]) == "k_conv_fwd_multi_t16" and r["ipb"] == 6 and r["img_fast"] == 1
+        assert r["grid"][0] == 768 // 6                                              # the image GROUP index fastest
+    assert p["fc_h_fwd"]["kernel"] == "k_fc_gemm_fwd" and p["fc_h_fwd"]["tiles"] == 48 and p["fc_h_fwd"]["S"] == 5
+    assert wgs(p["fc_h_fwd"]) == 240
+    assert p["fc_z_fwd"]["kernel"] == "k_nl_fwd3<4>"
+    assert p["fc_z_bwd"]["kernel"] == "k_nl_bwd<false>"
+    assert p["fc_h_bwd"]["kernel"] == "k_fc_gemm_bwd" and wgs(p["fc_h_bwd"]) == 416
+    assert p["conv3_dx"]["kernel"] == "k_conv_dx_t16_multi<GeomC3>" and p["conv2_dx"]["kernel"] == "k_conv_dx_t16_multi<GeomC2>"
+    assert p["conv3_dx"]["wt_t16"] == 1 and p["head"]["wt_t16"] == (1, 1)           # the tenants write the layout the kernel reads
+    assert p["conv_dw_all"]["ipb"] == (7, 7, 8) and wgs(p["conv_dw_all"]) == 249
+    assert p["fc_h_bwd"]["implicit_sigma"] == 1                                      # (the tiled GEMM carries it too)
+
+
+def test_data_efficient_reaches_the_kernels_of_design_3_3(emu):
+    p = plan(emu, **DATA_EFF)
+    assert p["conv1_fwd"]["kernel"] == "k_conv_fwd_lds<GeomD1>" and p["conv2_fwd"]["kernel"] == "k_conv_fwd_lds<GeomD2>"
+    assert "conv3_fwd" not in p
+    assert p["conv2_dx"]["kernel"] == "k_conv_dx_lds<GeomD2,MULTI=false>"
+    assert p["conv_dw_all"]["kernel"] == "k_conv_dw_all<2>" and p["conv_dw_all"]["nblocks"][2] == 0
+    # 2 * 256 * 576 = 0.3 M elements: under the 1 M threshold of the pairing
+    assert p["fc_h_bwd"]["implicit_sigma"] == 0
+    assert plan(emu, opts="implicit_small=1", **DATA_EFF)["fc_h_bwd"]["implicit_sigma"] == 1
+
+
+@pytest.mark.parametrize("cfg,kw", [(2, CANONICAL), (3, B256), (4, DATA_EFF)])
+def test_every_planned_kernel_is_in_the_recorded_profile_of_its_config(emu, cfg, kw):
+    recorded = recorded_kernels(cfg)
+    p = plan(emu, **kw)
+    for tag, row in p.items():
+        if tag == "caps" or tag.startswith("act_"):
+            continue
+        assert base(row["kernel"]) in recorded, (tag, row["kernel"])
+    # and the other way round: every step kernel of the learner that the profile shows is one the plan names
+    step = {"k_conv_fwd_t16", "k_conv_fwd_full", "k_conv_fwd_multi_t16", "k_conv_fwd_lds", "k_nl_fwd3", "k_fc_gemm_fwd", "k_head",
+            "k_nl_bwd", "k_fc_gemm_bwd", "k_conv_dx_lds", "k_conv_dx_t16_multi", "k_conv_dw_all", "k_reduce_conv_dw_all"}
+    planned = {base(r["kernel"]) for t, r in p.items() if t != "caps" and not t.startswith("act_")}
+    assert recorded & step == planned
+
+
+# ------------------------------------------------------------------------------------------------------ the thresholds
+def test_conv_forward_image_loop_starts_at_256_images(emu):
+    lo, hi = plan(emu, batch=85), plan(emu, batch=86)                                # 255 / 258 images
+    assert [base(lo["conv%d_fwd" % i]["kernel"]) for i in (1, 2, 3)] == ["k_conv_fwd_t16"] * 3
+    assert all(lo["conv%d_fwd" % i]["ipb"] == 1 for i in (1, 2, 3))
+    assert [base(hi["conv%d_fwd" % i]["kernel"]) for i in (1, 2, 3)] == ["k_conv_fwd_full", "k_conv_fwd_multi_t16", "k_conv_fwd_multi_t16"]
+    assert all(hi["conv%d_fwd" % i]["ipb"] > 1 for i in (1, 2, 3))
+
+
+def test_batch_64_conv_input_gradient_image_loop_and_the_forward_only_gemm(emu):
+    lo, hi = plan(emu, batch=63), plan(emu, batch=64)
+    for i in (2, 3):
+        assert base(lo["conv%d_dx" % i]["kernel"]) == "k_conv_dx_lds" and lo["conv%d_dx" % i]["ipb"] == 1
+        assert base(hi["conv%d_dx" % i]["kernel"]) == "k_conv_dx_t16_multi"
+    assert lo["head"]["wt_t16"] == (0, 0) and hi["head"]["wt_t16"] == (1, 1)
+    # the forward's online net carries 2B rows, the backward B: from 64 to 127 only the forward is on the tiled GEMM
+    assert lo["fc_h_fwd"]["kernel"] == "k_nl_fwd3<2>" and lo["fc_h_bwd"]["kernel"] == "k_nl_bwd<false>"
+    assert hi["fc_h_fwd"]["kernel"] == "k_fc_gemm_fwd" and hi["fc_h_bwd"]["kernel"] == "k_nl_bwd<false>"
+    assert hi["fc_h_bwd"]["gemm_bwd"] == 0
+
+
+def test_backward_gemm_starts_at_batch_128(emu):
+    lo, hi = plan(emu, batch=127), plan(emu, batch=128)
+    assert lo["fc_h_fwd"]["kernel"] == "k_fc_gemm_fwd" and lo["fc_h_bwd"]["kernel"] == "k_nl_bwd<false>" and lo["fc_h_bwd"]["gemm_bwd"] == 0
+    assert hi["fc_h_fwd"]["kernel"] == "k_fc_gemm_fwd" and hi["fc_h_bwd"]["kernel"] == "k_fc_gemm_bwd" and hi["fc_h_bwd"]["gemm_bwd"] == 1
+
+
+def test_batch_32_is_the_last_on_the_pipelined_and_tall_bodies(emu):
+    lo, hi = plan(emu, batch=32), plan(emu, batch=33)
+    assert lo["fc_z_bwd"]["pipe"] == 1 and lo["fc_z_bwd"]["z_tall"] == 1 and lo["fc_z_bwd"]["kernel"] == "k_nl_bwd<true>"
+    assert lo["fc_z_bwd"]["z_ct"] == 2 and lo["fc_h_bwd"]["h_ct"] == 4
+    assert hi["fc_z_bwd"]["pipe"] == 0 and hi["fc_z_bwd"]["z_tall"] == 0 and hi["fc_z_bwd"]["kernel"] == "k_nl_bwd<false>"
+    assert hi["fc_z_bwd"]["z_ct"] == 0 and hi["fc_h_bwd"]["h_ct"] == 0
+    # neither the pipelined body nor the tiled GEMM: the sigma gradient is stored
+    assert hi["fc_h_bwd"]["implicit_sigma"] == 0
+    # weight gradients: one image per workgroup up to 32, from 33 on the per-layer search.  At 33 images one image per workgroup
+    # is 3 * 33 + 2 * 33 + 2 * 33 = 231 workgroups, within one round of 256, and no choice has a shorter longest workgroup; the
+    # uniform count would be ceil(33 / 32) = 2, so the launch loses the image-fastest decode
+    assert lo["conv_dw_all"]["ipb"] == (1, 1, 1) and lo["conv_dw_all"]["img_fast"] == 1 and wgs(lo["conv_dw_all"]) == 224
+    assert hi["conv_dw_all"]["ipb"] == (1, 1, 1) and hi["conv_dw_all"]["img_fast"] == 0 and wgs(hi["conv_dw_all"]) == 231
+
+
+def test_short_and_long_histories(emu):
+    p3 = plan(emu, history=3)
+    assert p3["conv1_fwd"]["kernel"] == "k_conv_fwd_lds<GeomC1>"                     # K = 192: not the whole-K tile's 256
+    assert base(p3["conv2_fwd"]["kernel"]) == "k_conv_fwd_t16"
+    p5 = plan(emu, history=5)                                                        # no LDS conv kernel beyond history 4
+    for i in (1, 2, 3):
+        assert base(p5["conv%d_fwd" % i]["kernel"]) == "k_gemm"
+    assert base(p5["conv3_dx"]["kernel"]) == "k_gemm" and base(p5["conv2_dx"]["kernel"]) == "k_gemm"
+    assert base(p5["conv1_dw"]["kernel"]) == "k_gemm" and "conv_dw_all" not in p5
+    assert p5["fc_h_fwd"]["kernel"] == "k_nl_fwd3<2>" and p5["fc_h_bwd"]["kernel"] == "k_nl_bwd<false>"    # FC still streamed
+    assert "feat_block_copy" in p5 and "dfeat_finish" in p5 and p5["head"]["tenants"] == 0
+
+
+def test_one_row_f32_forward(emu):
+    p = plan(emu)
+    assert p["act_conv1_fwd"]["kernel"] == "k_conv_fwd_lds<GeomC1,F32SRC>"
+    assert base(p["act_conv2_fwd"]["kernel"]) == "k_conv_fwd_t16" and base(p["act_conv3_fwd"]["kernel"]) == "k_conv_fwd_t16"
+    assert p["act_fc_h_fwd"]["kernel"] == "k_nl_fwd3<2>" and p["act_fc_z_fwd"]["kernel"] == "k_nl_fwd3<2>"
+    assert p["act_conv1_fwd"]["img_fast"] == 0                                       # one image: no multiple of 8
+    d = plan(emu, **DATA_EFF)
+    assert d["act_conv1_fwd"]["kernel"] == "k_conv_fwd_lds<GeomD1,F32SRC>"
+
+
+@pytest.mark.parametrize("atoms,zi", [(51, 1), (64, 1), (65, 2), (128, 2), (129, 4)])
+def test_head_instantiation_follows_the_atom_count(emu, atoms, zi):
+    assert plan(emu, atoms=atoms)["head"]["kernel"] == "k_head<%d>" % zi
+
+
+# ------------------------------------------------------------------------------------------------ RB_OPTS
+def test_rb_opts_keys_reach_the_kernels_design_8_names(emu):
+    g1 = plan(emu, opts="generic=1")                                                 # every contraction on the fallback
+    for tag in ("conv1_fwd", "conv2_fwd", "conv3_fwd", "fc_h_fwd", "fc_z_fwd", "fc_z_dw", "fc_z_dx", "fc_h_dw", "fc_h_dx", "conv3_dx",
+                "conv2_dx", "conv1_dw", "conv2_dw", "conv3_dw"):
+        assert base(g1[tag]["kernel"]) == "k_gemm", tag
+    g2 = plan(emu, opts="generic=2")                                                 # the noisy-linear layers only
+    assert base(g2["conv1_fwd"]["kernel"]) == "k_conv_fwd_t16" and "conv_dw_all" in g2
+    for tag in ("fc_h_fwd", "fc_z_fwd", "fc_z_dw", "fc_z_dx", "fc_h_dw", "fc_h_dx"):
+        assert base(g2[tag]["kernel"]) == "k_gemm", tag
+    f0 = plan(emu, opts="fc_gemm=0", **B256)
+    assert f0["fc_h_fwd"]["kernel"] == "k_nl_fwd3<4>" and f0["fc_h_bwd"]["kernel"] == "k_nl_bwd<false>"
+    f1 = plan(emu, opts="fc_gemm=1")
+    assert f1["fc_h_fwd"]["kernel"] == "k_fc_gemm_fwd" and f1["fc_h_bwd"]["kernel"] == "k_fc_gemm_bwd"
+    c0 = plan(emu, opts="conv_full=0", **B256)                                       # the chunked kernel
+    assert c0["conv1_fwd"]["kernel"] == "k_conv_fwd_t16<GeomC1>"
+    assert base(c0["conv2_fwd"]["kernel"]) == "k_conv_fwd_multi_t16"
+    t0 = plan(emu, opts="t16=0")                                                     # the split-K kernel that history < 4 gets
+    assert t0["conv1_fwd"]["kernel"] == "k_conv_fwd_lds<GeomC1>" and base(t0["conv2_fwd"]["kernel"]) == "k_conv_fwd_t16"
+    i0 = plan(emu, opts="img_fast=0")
+    for tag in ("conv1_fwd", "conv2_fwd", "conv3_fwd", "conv3_dx", "conv2_dx", "conv_dw_all"):
+        assert i0[tag]["img_fast"] == 0, tag
+    assert i0["conv1_fwd"]["grid"] == (5, 1, 96)                                     # the image index slowest
+    d2 = plan(emu, opts="dx_ipb=2")
+    assert d2["conv3_dx"]["kernel"] == "k_conv_dx_t16_multi<GeomC3>" and d2["conv3_dx"]["ipb"] == 2
+    assert d2["conv2_dx"]["kernel"] == "k_conv_dx_t16_multi<GeomC2>" and d2["head"]["wt_t16"] == (1, 1)
+    e2 = plan(emu, opts="dx_ipb=2", **DATA_EFF)
+    assert e2["conv2_dx"]["kernel"] == "k_conv_dx_lds<GeomD2,MULTI=true>" and e2["conv2_dx"]["ipb"] == 2
+    m0 = plan(emu, opts="conv_multi=0", **B256)                                      # one image per workgroup
+    assert [base(m0["conv%d_fwd" % i]["kernel"]) for i in (1, 2, 3)] == ["k_conv_fwd_t16"] * 3
+    w = plan(emu, opts="dw_ipb0=2,dw_ipb1=4,dw_ipb2=8")
+    assert w["conv_dw_all"]["ipb"] == (2, 4, 8)
+    assert plan(emu, opts="xs=2")["fc_h_bwd"]["hsplits"] == 2
+
+
+def test_replica_exchange_defers_the_fc_weight_gradients(emu):
+    p = plan(emu, world=2)
+    assert "pack_factors" in p and p["fc_z_bwd"]["dw"] == (0, 0) and p["fc_h_bwd"]["dw"] == (0, 0)
+    assert p["fc_h_bwd"]["fuse_norm"] == 0 and p["fc_h_bwd"]["implicit_sigma"] == 0 and p["fc_z_bwd"]["pipe"] == 0
+
+
+def test_bad_arguments_are_refused_with_a_message(emu):
+    cfg = _lib.LearnerConfig(batch=32, atoms=51, actions=6, history=4, hidden=512, architecture=0, multi_step=3, v_min=-10.0,
+                             v_max=10.0, discount=0.99)
+    small = C.create_string_buffer(64)
+    assert emu.rb_debug_launch_plan(C.byref(cfg), None, 256, 0, 1, 0, small, 64) == -1      # RB_ERR_INVALID
+    assert b"too few" in emu.rb_last_error()
+    buf = C.create_string_buffer(1 << 14)
+    assert emu.rb_debug_launch_plan(C.byref(cfg), b"no_such_key=1", 256, 0, 1, 0, buf, 1 << 14) < 0
+    assert b"no_such_key" in emu.rb_last_error()

@@ -39,7 +39,7 @@ def test_generic_gemm_fallback_still_matches_golden(emu, monkeypatch):
 
 def test_row_split_input_gradient_matches_golden(emu, monkeypatch):
     """The hidden layer's input gradient split over 4 row ranges + k_dfeat_finish(splits = 4) — the shape the canonical
-    hidden-512 network runs (xs = 2H/256 = 4, learner.hip) — forced on the small canonical fixture with RB_OPTS=xs=4."""
+    hidden-512 network runs (xs = 2H/256 = 4, learner_plan.h plan_caps) — forced on the small canonical fixture with RB_OPTS=xs=4."""
     monkeypatch.setenv("RB_OPTS", "xs=4")
     name = "canon"
     ad = CAbiLearnAdapter(emu, NumpyMem(), name)

@@ -1,7 +1,7 @@
 # usage: bash tools/kernel_resources.sh [pattern] — VGPRs / spills / LDS / occupancy of every kernel of the library whose name matches
 PAT=${1:-.}
 cd rainbow_amd/csrc
-for f in learner.hip replay.hip; do
+for f in *.hip; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off --cuda-device-only -c $f -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 |
   python3 -c "
 import re, sys
