@@ -229,6 +229,37 @@ int rb_catch_stats(rb_catch_t* c, rb_catch_stats_t* out_host, rb_stream_t stream
 /* Zero those totals (stream-ordered, asynchronous). */
 int rb_catch_reset_stats(rb_catch_t* c, rb_stream_t stream);
 
+/* ================================================================ episode tally ==
+ * An environment-independent recorder of per-episode returns on the device (test.py:19-41 keeps the list T_rewards): fed with
+ * the rewards / nonterminals vectors every round already produces, so that an evaluation round on a device environment
+ * (act -> step -> tally) is launches on one stream with no synchronisation, like a training round.  Rewards are taken as they
+ * come: evaluation does not clip (test.py:28).
+ * Rules:
+ *  - S streams share `episodes` slots; stream s has the quota q_s = episodes / S + (s < episodes % S ? 1 : 0) — the quotas sum
+ *    to `episodes`, a stream may have quota 0 — so that N episodes are N / S per stream whatever their lengths (counting "the
+ *    first N to finish" would over-represent the streams whose episodes are short);
+ *  - per stream the tally keeps a running return (f32, ret = ret + r in step order), a running length (i32) and the number of
+ *    episodes it has recorded;
+ *  - a step adds rewards[s] and 1 to the running values of every stream; where nonterminals[s] == 0 the episode is recorded as
+ *    (return, length) if the stream is still under its quota, and the running values are zeroed either way: the reward of the
+ *    ending step belongs to the ending episode, episodes that finish after the quota is filled are ignored;
+ *  - remaining = sum over s of (q_s - recorded_s); 0 = all `episodes` slots are filled, further steps change nothing on record;
+ *  - the record is stream-major: the q_0 slots of stream 0 in the order its episodes ended, then stream 1's, and so on.  A slot
+ *    not yet filled reads as (return NaN, length 0); streams_host names the owning stream of every slot, filled or not.      */
+typedef struct rb_tally rb_tally_t;
+/* 1 <= streams <= 64, 1 <= episodes <= 65536.  The tally starts reset.  Synchronises the null stream. */
+int rb_tally_create(rb_tally_t** out, int32_t streams, int32_t episodes);
+int rb_tally_destroy(rb_tally_t* t);
+/* Start over: every slot unfilled, running values zero, remaining = episodes.  Asynchronous, one launch. */
+int rb_tally_reset(rb_tally_t* t, rb_stream_t stream);
+/* One step of every stream: rewards_dev f32[S], nonterminals_dev u8[S] (0 = this step ended the episode), read when the launch
+ * runs (stream order).  Asynchronous, one launch of one wave.                                                          */
+int rb_tally_step(rb_tally_t* t, const float* rewards_dev, const uint8_t* nonterminals_dev, rb_stream_t stream);
+/* Episodes still to be recorded.  SYNCHRONISES `stream`. */
+int rb_tally_remaining(rb_tally_t* t, int32_t* remaining_host, rb_stream_t stream);
+/* The record: returns_host f32, lengths_host i32, streams_host i32, [episodes] each, all three required.  SYNCHRONISES `stream`. */
+int rb_tally_read(rb_tally_t* t, float* returns_host, int32_t* lengths_host, int32_t* streams_host, rb_stream_t stream);
+
 /* SegmentTree.find (memory.py:64-82): float64 values against float32 nodes.       */
 int rb_replay_find(rb_replay_t* r, const double* values_dev, int32_t n, float* probs_dev,
                    int64_t* data_idx_dev, int64_t* tree_idx_dev, rb_stream_t stream);
@@ -398,6 +429,24 @@ int rb_learner_act_wait(rb_learner_t* l, const float* state_dev, int32_t noisy, 
  * caller a device-to-host copy: the values are final once the stream has drained.         */
 int rb_learner_act_batch(rb_learner_t* l, const float* states_dev, int32_t n, int32_t noisy,
                          int32_t* actions_dev, float* q_dev, rb_stream_t stream);
+
+/* rb_learner_act_batch with Agent.act_e_greedy's draw (agent.py:58-59; test.py:26 evaluates with epsilon = 0.001) inside the
+ * head kernel: the same forward, the same n range and buffer growth; only the action selection differs.  For image i of the
+ * call, with row = row0 + i:
+ *   (x0, x1, ., .) = Philox4x32-10(key = rng_seed, counter = (lo = rng_round, hi = row))     the generator of the device Catch
+ *   u = (float)(x0 >> 8) * 2^-24                                                              24 bits, in [0, 1)
+ *   explore iff u < epsilon (a float32 compare: epsilon = 0 never explores, epsilon >= 1 always does)
+ *   actions_dev[i] = x1 % actions if explored, else the greedy action of rb_learner_act_batch
+ *   q_dev[i] (optional) = the GREEDY action's value either way (what evaluate_q returns, agent.py:110-112)
+ *   explored_dev[i] (optional, u8) = 1 or 0
+ * The generator is counter-based and keeps no state on the device: the same (rng_seed, rng_round, row) gives the same draw
+ * again, and because a row's draw depends on row0 + i only, a caller that splits its states over several calls passes the
+ * offset of each part as row0 and gets what one call would have given.  n >= 2: the draw lives in the head kernel (no launch
+ * of its own); n == 1: the one-launch act path, then one wave that applies the draw to the stored action.
+ * Refused with RB_ERR_INVALID and a message: NaN or negative epsilon, NULL actions_dev, row0 < 0.                         */
+int rb_learner_act_batch_eps(rb_learner_t* l, const float* states_dev, int32_t n, int32_t noisy, float epsilon,
+                             uint64_t rng_seed, uint64_t rng_round, int32_t row0, int32_t* actions_dev, float* q_dev,
+                             uint8_t* explored_dev, rb_stream_t stream);
 
 /* Agent.learn minus sampling/optimiser (agent.py:66-96): three forwards, double-Q
  * select, C51 projection, weighted cross-entropy, full backward into grads_dev.

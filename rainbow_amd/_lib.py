@@ -88,6 +88,12 @@ SIGNATURES = {
     "rb_catch_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rb_catch_stats": (c_int, [c_void_p, C.POINTER(CatchStats), c_void_p]),
     "rb_catch_reset_stats": (c_int, [c_void_p, c_void_p]),
+    "rb_tally_create": (c_int, [C.POINTER(c_void_p), c_int32, c_int32]),
+    "rb_tally_destroy": (c_int, [c_void_p]),
+    "rb_tally_reset": (c_int, [c_void_p, c_void_p]),
+    "rb_tally_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rb_tally_remaining": (c_int, [c_void_p, C.POINTER(c_int32), c_void_p]),
+    "rb_tally_read": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rb_replay_find": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rb_replay_sample": (c_int, [c_void_p, c_int32, c_double, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -118,6 +124,8 @@ SIGNATURES = {
     "rb_learner_act": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "rb_learner_act_wait": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, C.POINTER(c_int32), C.POINTER(c_float), c_void_p]),
     "rb_learner_act_batch": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "rb_learner_act_batch_eps": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_uint64, c_uint64, c_int32, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
     "rb_learner_learn": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p]),
     "rb_learner_learn_windows": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,

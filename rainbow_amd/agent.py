@@ -368,11 +368,18 @@ class Agent:
         self._forward_single(state)
         return int(self._aq_act[0])
 
-    def act_batch(self, states, device_out=False):
+    def act_batch(self, states, device_out=False, epsilon=None, rng=(0, 0), row0=0):
         """Vectorised actors: `states` f32 [n, h, 84, 84] on the device (processed 2*batch_size at a time).
         Returns the n greedy actions (numpy int64), i.e. [self.act(s) for s in states] in one forward.
         device_out=True: the actions stay on the device — an int32 [n] tensor, final in stream order — and the call does NOT
-        synchronise (for an environment that lives on the device: rainbow_amd.envs, ReplayMemory.append_streams)."""
+        synchronise (for an environment that lives on the device: rainbow_amd.envs, ReplayMemory.append_streams).
+        epsilon (None = the greedy path, as before): act_e_greedy (agent.py:58-59) for every state, drawn in the head kernel
+        (rb_learner_act_batch_eps): state i explores iff its uniform from Philox(key = rng[0], counter = (lo = rng[1], hi = i))
+        is below epsilon, and then takes that block's second word modulo the action count.  rng = (seed, round): the caller
+        advances `round` once per call; a state's draw depends on (seed, round, row0 + i) only, not on the chunking here, and
+        a caller that splits one round's states over several calls passes the number of each part's first state as row0."""
+        if epsilon is not None:
+            return self._act_batch_eps(states, device_out, float(epsilon), rng, int(row0))
         self._flush_noise()
         st = states
         if st.dtype != torch.float32 or st.device != self.device or not st.is_contiguous():
@@ -397,6 +404,29 @@ class Agent:
             torch.cuda.current_stream(self.device).synchronize()
             out[lo:lo + m] = self._act_np[:m]
         return out
+
+    def _act_batch_eps(self, states, device_out, epsilon, rng, row0):
+        self._flush_noise()
+        st = states
+        if st.dtype != torch.float32 or st.device != self.device or not st.is_contiguous():
+            st = states.to(device=self.device, dtype=torch.float32).contiguous()
+        n = int(st.shape[0])
+        cap = int(self._act_np.shape[0])
+        noisy = 1 if self.training else 0
+        seed, rnd = int(rng[0]) & 0xFFFFFFFFFFFFFFFF, int(rng[1]) & 0xFFFFFFFFFFFFFFFF
+        acts = torch.empty(n, dtype=torch.int32, device=self.device) if device_out else None
+        out = None if device_out else np.empty(n, dtype=np.int64)
+        for lo in range(0, n, cap):
+            m = min(cap, n - lo)
+            dst = acts[lo:lo + m].data_ptr() if device_out else self._act_pin.data_ptr()
+            rc = self._lib.rb_learner_act_batch_eps(self._h, st[lo:lo + m].data_ptr(), m, noisy, epsilon, seed, rnd, row0 + lo, dst,
+                                                    None if device_out else self._q_pin.data_ptr(), None, self._stream())
+            if rc != 0:
+                L.check(self._lib, rc)
+            if not device_out:
+                torch.cuda.current_stream(self.device).synchronize()
+                out[lo:lo + m] = self._act_np[:m]
+        return acts if device_out else out
 
     def act_e_greedy(self, state, epsilon=0.001):
         """agent.py:58-59."""

@@ -193,4 +193,39 @@ int rb_learner_act_batch(rb_learner_t* l, const float* states_dev, int32_t n, in
   return RB_OK;
 }
 
+// rb_learner_act_batch with the e-greedy draw in the head (include/rainbow_hip.h): the same forward, the same buffers.
+int rb_learner_act_batch_eps(rb_learner_t* l, const float* states_dev, int32_t n, int32_t noisy, float epsilon, uint64_t rng_seed,
+                             uint64_t rng_round, int32_t row0, int32_t* actions_dev, float* q_dev, uint8_t* explored_dev,
+                             rb_stream_t stream) {
+  RB_REQUIRE(l && states_dev, "rb_learner_act_batch_eps: NULL argument");
+  RB_REQUIRE(actions_dev, "rb_learner_act_batch_eps: NULL actions_dev (the draw is applied to the stored action)");
+  RB_REQUIRE(epsilon >= 0.0f, "rb_learner_act_batch_eps: epsilon must be a number >= 0, got %g", (double)epsilon);
+  RB_REQUIRE(row0 >= 0, "rb_learner_act_batch_eps: row0 must be >= 0, got %d", (int)row0);
+  RB_REQUIRE(n >= 1 && n <= 4096, "rb_learner_act_batch_eps: n must be in [1, 4096]");
+  const Layout& L = l->L;
+  if (n == 1) {
+    // the one-launch act path, then one wave that applies the draw of row0 to the action it stored
+    const int rc1 = rb_learner_act_batch(l, states_dev, 1, noisy, actions_dev, q_dev, stream);
+    if (rc1 != RB_OK) return rc1;
+    RB_LAUNCH(k_act_eps_override, dim3(1), dim3(64), stream, L.A, epsilon, rng_seed, rng_round, (int)row0, actions_dev, explored_dev);
+    RB_LAUNCH_CHECK();
+    return RB_OK;
+  }
+  RB_FLUSH_UPDATE(l, stream);
+  {
+    int rc0 = ensure_rows(l, n);
+    if (rc0 != RB_OK) return rc0;
+  }
+  ImgSrc src;
+  memset(&src, 0, sizeof(src));
+  src.f32 = states_dev; src.B = n;
+  const NetPtrs on = net_ptrs(L, l->p_online, noisy ? l->n_online : l->zero_noise);
+  int rc = forward(l, n, 0, src, on, on, (hipStream_t)stream);
+  if (rc != RB_OK) return rc;
+  RB_LAUNCH(k_head_act_eps, dim3((unsigned)n), dim3(256), stream, L.Z, L.A, (const float*)l->logits, (const float*)l->support, epsilon,
+            rng_seed, rng_round, (int)row0, actions_dev, q_dev, explored_dev);
+  RB_LAUNCH_CHECK();
+  return RB_OK;
+}
+
 }  // extern "C"

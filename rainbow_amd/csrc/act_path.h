@@ -6,6 +6,7 @@
 // Same arithmetic as model.py:42-46,69-80 (f32, fused multiply-add accumulation in a fixed order).
 #pragma once
 #include "noisy_linear.h"
+#include "rb_common.h"
 #include "rb_device.h"
 
 #define RB_ACT_LDS 15360          // floats of input patch per workgroup (60 KB)
@@ -172,8 +173,26 @@ __device__ __forceinline__ float rb_dueling_q(const float* lg, const float* mean
 // and s_ev [A] workgroup scratch.  All threads of a 256-thread workgroup call.  err (optional): the word an expired in-launch
 // wait of launch number `err_epoch` sets to that number -> action -1 for THAT launch only (a later launch compares with its own
 // number: the failure state needs no reset and cannot stick).
+// epsilon >= 0 (rb_learner_act_batch_eps; the existing callers do not pass it): the e-greedy draw of agent.py:58-59 for row
+// `rng_row` happens here, in the thread that stores the action — rb_eps_draw below; q stays the GREEDY action's value.
+struct rb_eps_choice {
+  int explore;      // u < epsilon
+  int action;       // x1 % A (meaningful when explore)
+};
+// (x0, x1, ., .) = Philox4x32-10(key = seed, counter = (lo = round, hi = row)); u = (x0 >> 8) * 2^-24 in [0, 1); counter-based,
+// nothing is stored: the same (seed, round, row) always gives the same draw
+__device__ __forceinline__ rb_eps_choice rb_eps_draw(uint64_t seed, uint64_t round, int row, float epsilon, int A) {
+  const rb_philox_out r = rb_philox(seed, (uint64_t)row, round);
+  const float u = (float)(r.v[0] >> 8) * 0x1p-24f;
+  rb_eps_choice c;
+  c.explore = u < epsilon ? 1 : 0;
+  c.action = (int)(r.v[1] % (uint32_t)A);
+  return c;
+}
 __device__ __forceinline__ void rb_head_act_body(int Z, int A, const float* lg, const float* support, float* s_mean, float* s_ev,
-                                                 int32_t* action_out, float* q_out, const unsigned* err, unsigned err_epoch = 0u) {
+                                                 int32_t* action_out, float* q_out, const unsigned* err, unsigned err_epoch = 0u,
+                                                 float epsilon = -1.0f, uint64_t rng_seed = 0, uint64_t rng_round = 0, int rng_row = 0,
+                                                 uint8_t* explored_out = nullptr) {
   const int t = (int)threadIdx.x;
   const int lane = rb_lane(), wave = rb_wave(), nw = (int)(blockDim.x >> 6);
   for (int z = t; z < Z; z += (int)blockDim.x) {
@@ -207,6 +226,11 @@ __device__ __forceinline__ void rb_head_act_body(int Z, int A, const float* lg, 
 #else
     if (err && err_epoch != 0u && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == err_epoch) best = -1;   // a bounded in-launch wait of THIS launch expired: no action
 #endif
+    if (epsilon >= 0.0f) {
+      const rb_eps_choice c = rb_eps_draw(rng_seed, rng_round, rng_row, epsilon, A);
+      if (c.explore && best >= 0) best = c.action;
+      if (explored_out) *explored_out = (uint8_t)c.explore;
+    }
 #if !defined(RB_HOST_INTERP)
     // (action, q) as ONE aligned 8-byte word where the caller laid them out that way (rainbow_amd/agent.py _forward_single: a pinned
     // pair): a single system-scope store — both are there when the host sees the action change, and the launch ends one host-memory

@@ -269,3 +269,24 @@ __global__ __launch_bounds__(256) void k_head_act(int Z, int A, const float* log
   rb_head_act_body(Z, A, logits + (int64_t)row * (Z + A * Z), support, s_mean, s_ev, action_out ? action_out + blockIdx.x : nullptr,
                    q_out ? q_out + blockIdx.x : nullptr, nullptr);
 }
+
+// The same head with the e-greedy draw of agent.py:58-59 in it (rb_learner_act_batch_eps): workgroup i serves row0 + i of the
+// caller's numbering, so a stream's draw does not depend on how the caller chunks its states.
+__global__ __launch_bounds__(256) void k_head_act_eps(int Z, int A, const float* logits, const float* support, float epsilon,
+                                                       uint64_t rng_seed, uint64_t rng_round, int row0, int32_t* action_out,
+                                                       float* q_out, uint8_t* explored_out) {
+  __shared__ float s_mean[RB_MAX_ATOMS];
+  __shared__ float s_ev[RB_MAX_ACTIONS];
+  const int i = (int)blockIdx.x;
+  rb_head_act_body(Z, A, logits + (int64_t)i * (Z + A * Z), support, s_mean, s_ev, action_out + i, q_out ? q_out + i : nullptr, nullptr,
+                   0u, epsilon, rng_seed, rng_round, row0 + i, explored_out ? explored_out + i : nullptr);
+}
+// n == 1: the one-launch act path has written the greedy (action, q); one wave applies the draw of row `row` on top of it.
+// (An action below zero is the act path's error report and stays.)
+__global__ __launch_bounds__(64) void k_act_eps_override(int A, float epsilon, uint64_t rng_seed, uint64_t rng_round, int row,
+                                                          int32_t* action, uint8_t* explored_out) {
+  if (threadIdx.x != 0) return;
+  const rb_eps_choice c = rb_eps_draw(rng_seed, rng_round, row, epsilon, A);
+  if (c.explore && *action >= 0) *action = c.action;
+  if (explored_out) *explored_out = (uint8_t)c.explore;
+}

@@ -6,9 +6,14 @@ timesteps never reach the host, and no call in a round synchronises (Agent.learn
 call late, from pinned memory).  `env` is a rainbow_amd.envs environment (CatchVec) with as many streams as `mem`.
 
 `train_host_vec` is the same loop for S raw HOST emulators (ALE) behind a rainbow_amd.frames.FrameStackVec: the emulators write
-their u8 screens into the front end's pinned staging, one upload and one launch per round build all S frame stacks."""
+their u8 screens into the front end's pinned staging, one upload and one launch per round build all S frame stacks.
+
+`evaluate_vec` / `evaluate_host_vec` are the reference's evaluation (test.py:13-41) for the same two kinds of environment:
+epsilon-greedy actions drawn in the batched act path, the per-episode list of returns, `episodes` spread evenly over the streams."""
 import numpy as np
 import torch
+
+from .evaluate import EpisodeTally, stream_quotas
 
 
 def train_device(agent, mem, env, args, T_max, on_eval=None):
@@ -119,7 +124,9 @@ def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None):
 def evaluate_device(agent, env, episodes):
     """Mean episode return of the agent in eval() mode (test.py's loop without epsilon) on `env` — a fresh environment with
     its own seed — over at least `episodes` finished episodes, read from the totals the environment keeps on the device.
-    The episode count is polled (one synchronisation) every 11 rounds; the agent is left in the mode it came in."""
+    The episode count is polled (one synchronisation) every 11 rounds; the agent is left in the mode it came in.
+    This is a quick mean for a game whose episodes all have one length; `evaluate_vec` is the test.py-faithful evaluation
+    (epsilon-greedy, the per-episode list, an even share of the episodes per stream, any rainbow_amd.envs environment)."""
     was_training = agent.training
     agent.eval()
     S = env.streams
@@ -136,3 +143,105 @@ def evaluate_device(agent, env, episodes):
     if was_training:
         agent.train()
     return st["mean_return"]
+
+
+def _evaluation_result(agent, returns, lengths, val_mem):
+    rewards = [float(x) for x in returns]                                         # test.py:33 T_rewards
+    Qs = agent.evaluate_q_memory(val_mem) if val_mem is not None else None        # test.py:38-39
+    return dict(avg_reward=sum(rewards) / len(rewards), rewards=rewards, lengths=[int(x) for x in lengths],      # test.py:41
+                avg_Q=float(sum(float(q) for q in Qs) / len(Qs)) if Qs is not None else None, Qs=Qs)
+
+
+def evaluate_vec(agent, env, episodes, epsilon=0.001, seed=0, val_mem=None, poll_every=8, max_rounds=None):
+    """test.py:13-41 on `env`, a rainbow_amd.envs environment of S streams with a seed of its own: the agent in eval() mode,
+    act_e_greedy with `epsilon` for every stream (Agent.act_batch(epsilon=..., rng=(seed, round)): the draw happens in the head
+    kernel), raw rewards, and the list of episode returns the reference calls T_rewards.  A round is act -> env.step_device ->
+    EpisodeTally.step, launches only; the number of episodes still missing is polled (one synchronisation) every `poll_every`
+    rounds.  Stream s contributes its first episodes // S + (s < episodes % S) episodes, so short episodes are not
+    over-represented; the list is stream-major.  More than `max_rounds` rounds (None = no bound) raise RuntimeError.
+    Returns dict(avg_reward, rewards, lengths, avg_Q, Qs): `rewards` has exactly `episodes` entries; Qs is
+    agent.evaluate_q_memory(val_mem) (test.py:38-39) and avg_Q its mean when a validation memory is given, else None.
+    The agent is left in the mode it came in."""
+    S = env.streams
+    poll_every = max(1, int(poll_every))
+    was_training = agent.training
+    agent.eval()                                                                  # test.py:15 / main.py:168
+    try:
+        tally = EpisodeTally(S, episodes, env.device)
+        states = env.reset()
+        if S == 1:
+            states = states.unsqueeze(0)
+        rounds = 0
+        while True:
+            actions = agent.act_batch(states, device_out=True, epsilon=epsilon, rng=(seed, rounds))     # test.py:26
+            states, rewards, nonterminals = env.step_device(actions)              # test.py:27
+            tally.step(rewards, nonterminals)                                     # test.py:28,32-33
+            rounds += 1
+            last = max_rounds is not None and rounds >= max_rounds
+            if rounds % poll_every == 0 or last:
+                missing = tally.remaining()
+                if missing == 0:
+                    break
+                if last:
+                    raise RuntimeError("evaluate_vec: %d of %d episodes still unfinished after max_rounds = %d rounds"
+                                       % (missing, episodes, max_rounds))
+        returns, lengths, _ = tally.result()
+        tally.close()
+        return _evaluation_result(agent, returns, lengths, val_mem)
+    finally:
+        if was_training:
+            agent.train()
+
+
+def evaluate_host_vec(agent, emus, front, episodes, epsilon=0.001, seed=0, val_mem=None, max_rounds=None):
+    """The same protocol for S = len(emus) raw host emulators behind `front`, a rainbow_amd.frames.FrameStackVec, duck-typed as
+    in train_host_vec.  The emulators are the caller's EVALUATION ones: env.py's eval mode reports no life-loss terminals
+    (env.py:70-75 is training only), so a step that reports life_lost raises ValueError.  A stream whose step ended its game
+    is reset in the same round with front.RESET.  Rewards are host values here, so the tally rule of rb_tally_* (even quotas,
+    f32 running return, the ending step's reward belongs to the ending episode, stream-major list) is kept in numpy.
+    Returns what evaluate_vec returns; more than `max_rounds` rounds raise RuntimeError."""
+    S = len(emus)
+    if S != front.streams:
+        raise ValueError("evaluate_host_vec: %d emulators, a front end of %d streams" % (S, front.streams))
+    quotas = stream_quotas(S, episodes)
+    if not 1 <= int(episodes) <= 65536:
+        raise ValueError("evaluate_host_vec: episodes must be in [1, 65536], got %d" % episodes)
+    recorded = [[] for _ in range(S)]
+    ret, length = np.zeros(S, dtype=np.float32), np.zeros(S, dtype=np.int64)
+    flags = np.zeros(S, dtype=np.uint8)
+    was_training = agent.training
+    agent.eval()
+    try:
+        scr = front.screens
+        for s in range(S):
+            emus[s].reset(scr[s, 0])
+        states = front.reset_all()
+        missing, rounds = int(episodes), 0
+        while missing > 0:
+            if max_rounds is not None and rounds >= max_rounds:
+                raise RuntimeError("evaluate_host_vec: %d of %d episodes still unfinished after max_rounds = %d rounds"
+                                   % (missing, episodes, max_rounds))
+            actions = agent.act_batch(states, epsilon=epsilon, rng=(seed, rounds))              # test.py:26
+            scr = front.screens
+            for s in range(S):
+                f, r, done, life_lost = emus[s].step(int(actions[s]), scr[s, 0], scr[s, 1])     # test.py:27
+                if life_lost:
+                    raise ValueError("evaluate_host_vec: emulator %d reported a lost life as an episode end; evaluation "
+                                     "needs emulators in evaluation mode (env.py:70-75 applies to training only)" % s)
+                ret[s] = ret[s] + np.float32(r)                                                  # test.py:28, unclipped
+                length[s] += 1
+                if done:
+                    if len(recorded[s]) < quotas[s]:
+                        recorded[s].append((ret[s], length[s]))                                 # test.py:33
+                        missing -= 1
+                    ret[s], length[s] = 0.0, 0
+                    emus[s].reset(scr[s, 0])                                                    # test.py:23-24, in the same round
+                    f = front.RESET
+                flags[s] = f
+            states = front.step(flags)
+            rounds += 1
+        flat = [x for per_stream in recorded for x in per_stream]
+        return _evaluation_result(agent, [x[0] for x in flat], [x[1] for x in flat], val_mem)
+    finally:
+        if was_training:
+            agent.train()

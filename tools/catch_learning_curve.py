@@ -2,7 +2,9 @@
 randomness (device Philox sampler and noise, lazy reset_noise, deferred optimiser pass, beta annealing, target syncs — all
 defaults) through rainbow_amd.loop.train_device, with the options tests/golden/make_golden_catch.py gives the reference.
 Every --t-eval env steps the agent is evaluated in eval() mode over 256 episodes on a fresh environment with a fixed seed.
-One line per checkpoint; `--no-learn` runs the same loop with learn() skipped (what an agent that does not learn scores)."""
+One line per checkpoint; `--no-learn` runs the same loop with learn() skipped (what an agent that does not learn scores).
+`--protocol vec` evaluates with rainbow_amd.loop.evaluate_vec instead (test.py's protocol: epsilon 0.001, 256 episodes spread
+evenly over the streams); the default, `device`, is evaluate_device as before."""
 import argparse
 import os
 import sys
@@ -26,10 +28,10 @@ def options(t_max, dev):
         model=None, T_max=t_max)
 
 
-def run(S, seed, t_max, t_eval, learn, dev):
+def run(S, seed, t_max, t_eval, learn, dev, protocol="device"):
     from rainbow_amd.agent import Agent
     from rainbow_amd.envs import CatchVec
-    from rainbow_amd.loop import evaluate_device, train_device
+    from rainbow_amd.loop import evaluate_device, evaluate_vec, train_device
     from rainbow_amd.memory import ReplayMemory
     args = options(t_max, dev)
     args.evaluation_interval = t_eval
@@ -45,7 +47,10 @@ def run(S, seed, t_max, t_eval, learn, dev):
 
     def on_eval(T):
         ev = CatchVec(16, dev, seed=EVAL_SEED)
-        curve.append((T, evaluate_device(agent, ev, 256)))
+        if protocol == "vec":
+            curve.append((T, evaluate_vec(agent, ev, 256, seed=T)["avg_reward"]))
+        else:
+            curve.append((T, evaluate_device(agent, ev, 256)))
         ev.close()
 
     t0 = time.perf_counter()
@@ -68,13 +73,14 @@ def main():
     ap.add_argument("--streams", type=int, nargs="+", default=[1, 16])
     ap.add_argument("--seeds", type=int, default=5)
     ap.add_argument("--no-learn", action="store_true")
+    ap.add_argument("--protocol", choices=["device", "vec"], default="device")
     a = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
     dev = torch.device("cuda", 0)
     for S in a.streams:
         for k in range(a.seeds if S == 1 else min(3, a.seeds)):
-            run(S, 101 + 7 * k, a.t_max, a.t_eval, not a.no_learn, dev)
+            run(S, 101 + 7 * k, a.t_max, a.t_eval, not a.no_learn, dev, a.protocol)
 
 
 if __name__ == "__main__":
