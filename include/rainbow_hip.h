@@ -448,6 +448,36 @@ int rb_learner_act_batch_eps(rb_learner_t* l, const float* states_dev, int32_t n
                              uint64_t rng_seed, uint64_t rng_round, int32_t row0, int32_t* actions_dev, float* q_dev,
                              uint8_t* explored_dev, rb_stream_t stream);
 
+/* One noise sample PER ROW for the batched act path (vectorised actors: stream s explores with its own perturbation of the
+ * weights; the reference has one environment and never meets the question).  Fills the caller-owned noise_rows_dev, f32
+ * [rows][n_noise]: every row has the layout of rb_learner_noise_layout, n_noise from rb_learner_sizes (its padding included);
+ * floats of a row that no tensor of the layout covers are written as zero.  rows in [1, 256], row0 >= 0.
+ * raw_normals_dev != NULL (parity hook, as in rb_learner_reset_noise): f32 [rows][rb_learner_noise_draws] of N(0,1) draws in
+ * the reference's order; row i is written from its own block.
+ * raw_normals_dev == NULL: the device Philox + Box-Muller of rb_learner_reset_noise — the same f(x) = sign(x) sqrt|x|, the same
+ * two normals per Philox block — keyed WITHOUT any device state: for row r = row0 + i, draws 2j and 2j + 1 come from
+ *   Philox4x32-10(key = rng_seed, counter = (hi = rng_round, lo = ((uint64)r << 32) | j)).
+ * The learner's own epoch counter is neither read nor advanced (learner resamples and graph replays are untouched); a row's
+ * values depend on (rng_seed, rng_round, r) only, so a caller that splits its rows over several calls passes each part's first
+ * row as row0 and gets what one call would have given.
+ * Refused with RB_ERR_INVALID and a message naming the argument, before anything is launched: NULL l or noise_rows_dev, rows
+ * outside [1, 256], row0 < 0.                                                                                            */
+int rb_learner_noise_rows(rb_learner_t* l, int32_t rows, int32_t row0, uint64_t rng_seed, uint64_t rng_round,
+                          const float* raw_normals_dev, float* noise_rows_dev, rb_stream_t stream);
+/* The forward of rb_learner_act_batch (training mode) with row i's noisy layers under noise row i of noise_rows_dev (f32
+ * [n][n_noise], as rb_learner_noise_rows writes it): states f32[n][history][7056], 1 <= n <= 256 (beyond the learn step's
+ * 3*batch images the forward buffers are regrown once, synchronising; the first call also allocates two scaled-activation
+ * buffers).  actions_dev i32[n], q_dev f32[n]: either may be NULL, both may be pinned host memory.  n == 1 runs the same
+ * kernels (not the one-launch act path).  The noisy layers are computed in the factorised form
+ *   y[m][j] = sum_k x[m][k] mu[j][k] + eo[m][j] * sum_k (x[m][k] ein[m][k]) sigma[j][k] + bmu[j] + bsigma[j] eo[m][j]
+ * so that mu and sigma are streamed ONCE for all rows; this is not the rounding order of the reference (model.py:39,44 forms
+ * W = mu + sigma * (eo ein^T) per sample, then contracts) — q agrees with the per-row reference within the act tolerance
+ * (rtol 2e-5, atol 1e-6), not to the bit, and an all-zero noise row gives rb_learner_act_batch(noisy = 0) within the same.
+ * Refused with RB_ERR_INVALID and a message naming the argument, before anything is launched: NULL l, states_dev or
+ * noise_rows_dev, n outside [1, 256].                                                                                    */
+int rb_learner_act_batch_rows(rb_learner_t* l, const float* states_dev, int32_t n, const float* noise_rows_dev,
+                              int32_t* actions_dev, float* q_dev, rb_stream_t stream);
+
 /* Agent.learn minus sampling/optimiser (agent.py:66-96): three forwards, double-Q
  * select, C51 projection, weighted cross-entropy, full backward into grads_dev.
  * Inputs are rb_replay_sample's outputs.  loss_dev f32[B] = per-sample CE (agent.py:94),

@@ -126,6 +126,8 @@ SIGNATURES = {
     "rb_learner_act_batch": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "rb_learner_act_batch_eps": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_uint64, c_uint64, c_int32, c_void_p, c_void_p,
                                          c_void_p, c_void_p]),
+    "rb_learner_noise_rows": (c_int, [c_void_p, c_int32, c_int32, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "rb_learner_act_batch_rows": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rb_learner_learn": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p]),
     "rb_learner_learn_windows": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -189,6 +189,7 @@ class Agent:
 
         self._init_parameters(float(getattr(args, "noisy_std", 0.1)))
         self._noise_pending = False
+        self._noise_rows, self._noise_rows_drawn, self._raw_rows = None, 0, None     # reset_noise_rows: one noise sample per row
         self.reset_noise()                                           # NoisyLinear.__init__ (model.py:23)
         if getattr(args, "model", None):                             # agent.py:26-36
             if os.path.isfile(args.model):
@@ -368,7 +369,61 @@ class Agent:
         self._forward_single(state)
         return int(self._aq_act[0])
 
-    def act_batch(self, states, device_out=False, epsilon=None, rng=(0, 0), row0=0):
+    def reset_noise_rows(self, rows, rng=(0, 0), raw_normals=None):
+        """One noise sample per ROW for act_batch(per_row_noise=True): fills the agent-owned [rows, n_noise] device tensor
+        (regrown when `rows` grows), a launch in stream order and no synchronisation.  rng = (seed, round): row r is drawn
+        from Philox(key = seed, counter = (hi = round, lo = (r << 32) | pair)) — it depends on (seed, round, r) only; the
+        learner's own noise generator (reset_noise, learn) is neither read nor advanced.  raw_normals (parity hook): float32
+        [rows, noise draws] of N(0,1) in the reference's order, one block per row.  The rows are redrawn before use and are
+        not part of state_dict / checkpoints."""
+        rows = int(rows)
+        if rows < 1:
+            raise ValueError("reset_noise_rows: rows must be >= 1, got %d" % rows)
+        n_noise = int(self.noise.numel())
+        if self._noise_rows is None or int(self._noise_rows.shape[0]) < rows:
+            self._noise_rows = torch.zeros((rows, n_noise), dtype=torch.float32, device=self.device)
+        raw = None
+        if raw_normals is not None:
+            raw = raw_normals.to(device=self.device, dtype=torch.float32).contiguous()
+            draws = int(self._lib.rb_learner_noise_draws(C.byref(self._cfg)))
+            if tuple(raw.shape) != (rows, draws):
+                raise ValueError("reset_noise_rows: raw_normals must be [%d, %d], got %s" % (rows, draws, tuple(raw.shape)))
+            self._raw_rows = raw                      # kept alive until the stream has consumed it
+        seed, rnd = int(rng[0]) & 0xFFFFFFFFFFFFFFFF, int(rng[1]) & 0xFFFFFFFFFFFFFFFF
+        for lo in range(0, rows, 256):
+            m = min(256, rows - lo)
+            rc = self._lib.rb_learner_noise_rows(self._h, m, lo, seed, rnd, raw[lo:lo + m].data_ptr() if raw is not None else None,
+                                                 self._noise_rows[lo:lo + m].data_ptr(), self._stream())
+            if rc != 0:
+                L.check(self._lib, rc)
+        self._noise_rows_drawn = rows
+
+    def _act_batch_rows(self, states, device_out, row0):
+        st = states
+        if st.dtype != torch.float32 or st.device != self.device or not st.is_contiguous():
+            st = states.to(device=self.device, dtype=torch.float32).contiguous()
+        n = int(st.shape[0])
+        if row0 < 0:
+            raise ValueError("act_batch: row0 must be >= 0, got %d" % row0)
+        if row0 + n > self._noise_rows_drawn:
+            raise ValueError("act_batch(per_row_noise=True): states %d .. %d need noise rows, reset_noise_rows drew %d"
+                             % (row0, row0 + n - 1, self._noise_rows_drawn))
+        cap = min(int(self._act_np.shape[0]), 256)
+        acts = torch.empty(n, dtype=torch.int32, device=self.device) if device_out else None
+        out = None if device_out else np.empty(n, dtype=np.int64)
+        for lo in range(0, n, cap):
+            m = min(cap, n - lo)
+            dst = acts[lo:lo + m].data_ptr() if device_out else self._act_pin.data_ptr()
+            rc = self._lib.rb_learner_act_batch_rows(self._h, st[lo:lo + m].data_ptr(), m, self._noise_rows[row0 + lo:row0 + lo + m].data_ptr(),
+                                                     dst, None if device_out else self._q_pin.data_ptr(), self._stream())
+            if rc != 0:
+                L.check(self._lib, rc)
+            if not device_out:
+                torch.cuda.current_stream(self.device).synchronize()
+                out[lo:lo + m] = self._act_np[:m]
+        return acts if device_out else out
+
+    def act_batch(self, states, device_out=False, epsilon=None, rng=(0, 0), row0=0, per_row_noise=False):
         """Vectorised actors: `states` f32 [n, h, 84, 84] on the device (processed 2*batch_size at a time).
         Returns the n greedy actions (numpy int64), i.e. [self.act(s) for s in states] in one forward.
         device_out=True: the actions stay on the device — an int32 [n] tensor, final in stream order — and the call does NOT
@@ -377,7 +432,15 @@ class Agent:
         (rb_learner_act_batch_eps): state i explores iff its uniform from Philox(key = rng[0], counter = (lo = rng[1], hi = i))
         is below epsilon, and then takes that block's second word modulo the action count.  rng = (seed, round): the caller
         advances `round` once per call; a state's draw depends on (seed, round, row0 + i) only, not on the chunking here, and
-        a caller that splits one round's states over several calls passes the number of each part's first state as row0."""
+        a caller that splits one round's states over several calls passes the number of each part's first state as row0.
+        per_row_noise=True (training mode): state i runs the noisy layers under noise row row0 + i of the last
+        reset_noise_rows() (rb_learner_act_batch_rows: every stream of a vectorised actor explores with its own draw); the
+        result does not depend on the chunking.  In eval() mode the flag is ignored (no noise at all); together with
+        `epsilon`, or with fewer rows drawn than states passed, it raises ValueError."""
+        if per_row_noise and epsilon is not None:
+            raise ValueError("act_batch: per_row_noise and epsilon cannot be combined")
+        if per_row_noise and self.training:
+            return self._act_batch_rows(states, device_out, int(row0))
         if epsilon is not None:
             return self._act_batch_eps(states, device_out, float(epsilon), rng, int(row0))
         self._flush_noise()

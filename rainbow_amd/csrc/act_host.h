@@ -193,6 +193,104 @@ int rb_learner_act_batch(rb_learner_t* l, const float* states_dev, int32_t n, in
   return RB_OK;
 }
 
+// The scaled-activation buffers of the per-row-noise path live beside the forward buffers: grown on demand (synchronising; once per size)
+static int ensure_rows_scaled(rb_learner* l, int rows) {
+  if (rows <= l->rows_s_cap) return RB_OK;
+  const Layout& L = l->L;
+  if (l->feat_s || l->h_s) RB_HIP_TRY(hipDeviceSynchronize());   // (a launch in flight may still read what is freed below)
+  float** bufs[2] = {&l->feat_s, &l->h_s};
+  const int64_t counts[2] = {(int64_t)rows * (2 * L.F + 16), (int64_t)rows * (2 * L.H + 16)};
+  for (int i = 0; i < 2; ++i) {
+    if (*bufs[i]) rb_dev_free(*bufs[i]);
+    *bufs[i] = nullptr;
+    hipError_t e = rb_dev_malloc((void**)bufs[i], (size_t)counts[i] * 4);
+    if (e != hipSuccess) {
+      l->rows_s_cap = 0;
+      rb_set_error("rb_learner_act_batch_rows: hipMalloc(%lld B) failed: %s", (long long)counts[i] * 4, hipGetErrorString(e));
+      return RB_ERR_OOM;
+    }
+  }
+  l->rows_s_cap = rows;
+  return RB_OK;
+}
+
+// rb_learner_act_batch with row i's noisy layers under noise row i (include/rainbow_hip.h; noisy_rows.h has the arithmetic)
+int rb_learner_act_batch_rows(rb_learner_t* l, const float* states_dev, int32_t n, const float* noise_rows_dev, int32_t* actions_dev,
+                              float* q_dev, rb_stream_t stream) {
+  RB_REQUIRE(l != nullptr, "rb_learner_act_batch_rows: NULL handle (l)");
+  RB_REQUIRE(states_dev != nullptr, "rb_learner_act_batch_rows: NULL states_dev");
+  RB_REQUIRE(noise_rows_dev != nullptr, "rb_learner_act_batch_rows: NULL noise_rows_dev");
+  RB_REQUIRE(n >= 1 && n <= 256, "rb_learner_act_batch_rows: n must be in [1, 256], got %d", (int)n);
+  RB_FLUSH_UPDATE(l, stream);
+  const Layout& L = l->L;
+  {
+    int rc0 = ensure_rows(l, n);
+    if (rc0 != RB_OK) return rc0;
+  }
+  const ActRowsPlan p = plan_act_rows(plan_in(l), n);
+  if (p.kernel != ACT_ROWS_GENERIC) {
+    int rc0 = ensure_rows_scaled(l, n);
+    if (rc0 != RB_OK) return rc0;
+  }
+  ImgSrc src;
+  memset(&src, 0, sizeof(src));
+  src.f32 = states_dev; src.B = n;
+  const NetPtrs on = net_ptrs(L, l->p_online, l->zero_noise);     // (the conv layers carry no noise)
+  for (int layer = 0; layer < L.nconv; ++layer) {
+    int rc = conv_fwd(l, layer, n, 0, src, on, on, (hipStream_t)stream);
+    if (rc != RB_OK) return rc;
+  }
+  const float* feat = l->act[L.nconv - 1];
+  const int nn = (int)L.n_noise;
+  if (p.kernel == ACT_ROWS_GENERIC) {
+    NlRowsGenericArgs h;
+    h.x = feat; h.ldx = L.F; h.mu = on.h_mu; h.sigma = on.h_sigma; h.bmu = on.h_bmu; h.bsigma = on.h_bsigma;
+    h.noise_rows = noise_rows_dev; h.n_noise = nn; h.ein_off = (int)L.h_ein; h.eout_off = (int)L.h_eout;
+    h.M = n; h.N = 2 * L.H; h.K = L.F; h.split_row = L.H; h.x_off1 = 0; h.ein_off1 = L.F;
+    h.out = l->h; h.ld_out = 2 * L.H; h.relu = 1;
+    RB_LAUNCH_T("fc_h_rows:k_nlr_generic", k_nlr_generic, p.hgrid, dim3(p.block), stream, h);
+    RB_LAUNCH_CHECK();
+    NlRowsGenericArgs z;
+    z.x = l->h; z.ldx = 2 * L.H; z.mu = on.z_mu; z.sigma = on.z_sigma; z.bmu = on.z_bmu; z.bsigma = on.z_bsigma;
+    z.noise_rows = noise_rows_dev; z.n_noise = nn; z.ein_off = (int)L.z_ein; z.eout_off = (int)L.z_eout;
+    z.M = n; z.N = L.NZ; z.K = L.H; z.split_row = L.Z; z.x_off1 = L.H; z.ein_off1 = L.H;
+    z.out = l->logits; z.ld_out = L.NZ; z.relu = 0;
+    RB_LAUNCH_T("fc_z_rows:k_nlr_generic", k_nlr_generic, p.zgrid, dim3(p.block), stream, z);
+    RB_LAUNCH_CHECK();
+  } else {
+    RB_LAUNCH(k_block_copy_rows, p.copy_grid, dim3(256), stream, feat, (int)n, L.F, noise_rows_dev, nn, (int)L.h_ein, l->feat_b, l->feat_s);
+    RB_LAUNCH_CHECK();
+    NlRowsArgs h;
+    h.x = l->feat_b; h.xs = l->feat_s; h.mu = on.h_mu; h.sigma = on.h_sigma; h.bmu = on.h_bmu; h.bsigma = on.h_bsigma;
+    h.noise_rows = noise_rows_dev; h.n_noise = nn; h.eout_off = (int)L.h_eout;
+    h.M = n; h.K = L.F; h.n_groups = 2;
+    h.grp[0] = NlRowGroup{0, L.H, 0, 0, 0};
+    h.grp[1] = NlRowGroup{L.H, L.H, 0, L.F, (int)rb_div_up(L.H, 16)};
+    h.out = l->h; h.out_blocked = l->h_b; h.out_scaled = l->h_s; h.next_ein_off = (int)L.z_ein; h.ld_out = 2 * L.H; h.relu = 1;
+    NlRowsArgs z;
+    z.x = l->h_b; z.xs = l->h_s; z.mu = on.z_mu; z.sigma = on.z_sigma; z.bmu = on.z_bmu; z.bsigma = on.z_bsigma;
+    z.noise_rows = noise_rows_dev; z.n_noise = nn; z.eout_off = (int)L.z_eout;
+    z.M = n; z.K = L.H; z.n_groups = 2;
+    z.grp[0] = NlRowGroup{0, L.Z, 0, 0, 0};
+    z.grp[1] = NlRowGroup{L.Z, L.NZ - L.Z, L.H, L.H, (int)rb_div_up(L.Z, 16)};
+    z.out = l->logits; z.out_blocked = nullptr; z.out_scaled = nullptr; z.next_ein_off = 0; z.ld_out = L.NZ; z.relu = 0;
+    if (p.kernel == ACT_ROWS_NLR_1) {
+      RB_LAUNCH_T("fc_h_rows:k_nlr_fwd", k_nlr_fwd<1>, p.hgrid, dim3(p.block), stream, h);
+      RB_LAUNCH_CHECK();
+      RB_LAUNCH_T("fc_z_rows:k_nlr_fwd", k_nlr_fwd<1>, p.zgrid, dim3(p.block), stream, z);
+    } else {
+      RB_LAUNCH_T("fc_h_rows:k_nlr_fwd", k_nlr_fwd<2>, p.hgrid, dim3(p.block), stream, h);
+      RB_LAUNCH_CHECK();
+      RB_LAUNCH_T("fc_z_rows:k_nlr_fwd", k_nlr_fwd<2>, p.zgrid, dim3(p.block), stream, z);
+    }
+    RB_LAUNCH_CHECK();
+  }
+  RB_LAUNCH(k_head_act, dim3((unsigned)n), dim3(256), stream, L.Z, L.A, (const float*)l->logits, 0, (const float*)l->support,
+            actions_dev, q_dev);
+  RB_LAUNCH_CHECK();
+  return RB_OK;
+}
+
 // rb_learner_act_batch with the e-greedy draw in the head (include/rainbow_hip.h): the same forward, the same buffers.
 int rb_learner_act_batch_eps(rb_learner_t* l, const float* states_dev, int32_t n, int32_t noisy, float epsilon, uint64_t rng_seed,
                              uint64_t rng_round, int32_t row0, int32_t* actions_dev, float* q_dev, uint8_t* explored_dev,

@@ -17,6 +17,7 @@
 // This file keeps the handle's lifecycle and the step itself (learn_impl, train_step_impl and their entry points).  Its sections:
 //   learner_internal.h  layout, RB_OPTS, the handle          learner_plan.h     which kernel a shape reaches (pure functions)
 //   head.h / grad_finish.h / adam_kernels.h / noise_kernel.h  kernels           conv_dispatch.h / fc_dispatch.h   the launches
+//   noisy_rows.h  the per-row-noise act layers (kernels)
 //   optimizer_host.h / act_host.h / exchange_host.h / layout_api.h / launch_plan_debug.h   the other entry points, by concern
 // Each is included HERE and nowhere else (they define non-template kernels and static functions).
 #include "learner_internal.h"
@@ -28,6 +29,7 @@
 #include "conv_dispatch.h"
 #include "fc_dispatch.h"
 #include "optimizer_host.h"
+#include "noisy_rows.h"
 #include "act_host.h"
 #include "exchange_host.h"
 #include "layout_api.h"
@@ -69,7 +71,7 @@ int rb_learner_destroy(rb_learner_t* l) {
   float** owned[] = {&l->feat_b, &l->h_b, &l->act[0], &l->act[1], &l->act[2], &l->dact[0], &l->dact[1], &l->dact[2], &l->hpart, &l->h,
                      &l->logits, &l->dlogits, &l->dlogitsT, &l->dh, &l->dhT, &l->dfeat_part, &l->dw_part[0], &l->dw_part[1], &l->dw_part[2],
                      &l->conv_wT[0], &l->conv_wT[1], &l->conv_wT[2],
-                     &l->log_ps_a, &l->pns_a, &l->m, &l->support, &l->zero_noise, &l->norm_part, &l->gemm_part, &l->noise_snap};
+                     &l->log_ps_a, &l->pns_a, &l->m, &l->support, &l->zero_noise, &l->norm_part, &l->gemm_part, &l->noise_snap, &l->feat_s, &l->h_s};
   for (float** p : owned)
     if (*p) rb_dev_free(*p);
   if (l->a_star) rb_dev_free(l->a_star);
@@ -134,6 +136,22 @@ int rb_learner_reset_noise(rb_learner_t* l, int32_t which, const float* raw_norm
   float* noise2 = which == 2 ? l->n_target : nullptr;
   RB_LAUNCH(k_noise, dim3((unsigned)rb_div_up(map.seg_begin[8], 256), which == 2 ? 2u : 1u), dim3(256), stream, noise, noise2,
             raw_normals_dev, map, l->seed, l->noise_ctr);
+  RB_LAUNCH_CHECK();
+  return RB_OK;
+}
+
+// One noise sample per ROW for rb_learner_act_batch_rows (include/rainbow_hip.h; noisy_rows.h k_noise_rows): keyed by (seed, round,
+// row) alone — the learner's epoch counter is neither read nor advanced.
+int rb_learner_noise_rows(rb_learner_t* l, int32_t rows, int32_t row0, uint64_t rng_seed, uint64_t rng_round,
+                          const float* raw_normals_dev, float* noise_rows_dev, rb_stream_t stream) {
+  RB_REQUIRE(l != nullptr, "rb_learner_noise_rows: NULL handle (l)");
+  RB_REQUIRE(noise_rows_dev != nullptr, "rb_learner_noise_rows: NULL noise_rows_dev");
+  RB_REQUIRE(rows >= 1 && rows <= 256, "rb_learner_noise_rows: rows must be in [1, 256], got %d", (int)rows);
+  RB_REQUIRE(row0 >= 0, "rb_learner_noise_rows: row0 must be >= 0, got %d", (int)row0);
+  const NoiseMap map = noise_map(l->L);
+  const int n_noise = (int)l->L.n_noise;
+  RB_LAUNCH(k_noise_rows, dim3((unsigned)rb_div_up(n_noise, 256), (unsigned)rows), dim3(256), stream, noise_rows_dev,
+            raw_normals_dev, map, n_noise, rng_seed, rng_round, (int)row0);
   RB_LAUNCH_CHECK();
   return RB_OK;
 }

@@ -178,6 +178,9 @@ struct rb_learner {
   float* hpart;         // [hs][NI][2H]
   float* h;             // [NI][2H]
   float *feat_b, *h_b;  // k-blocked copies of feat [NI][F] and h [NI][2H] for the streamed forward kernels
+  float *feat_s, *h_s;  // k-blocked SCALED copies for the per-row-noise act path (noisy_rows.h): feat (.) ein_hv | feat (.) ein_ha
+                        // [rows_s_cap][2F] and h (.) ein_z [rows_s_cap][2H]; allocated by the first rb_learner_act_batch_rows
+  int rows_s_cap;
   float* logits;        // [NI][NZ]
   float* dlogits;       // [B][NZ]
   float* dlogitsT;      // [NZ][B]: the same, transposed (the output layer's input gradient reads its dY operand from it)

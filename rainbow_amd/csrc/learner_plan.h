@@ -385,6 +385,37 @@ static FcFwdPlan plan_fc_fwd(const PlanIn& in, int n_on, int n_tg) {
   return p;
 }
 
+// The noisy layers of rb_learner_act_batch_rows (noisy_rows.h: one noise sample per row, n <= 256 rows of the online net): the
+// streamed two-contraction kernel where k_nl_fwd3's preconditions hold, in 16-row m-chunks up to 16 rows and 32-row ones beyond (its
+// accumulators and reduction buffer are twice fwd3's: no 64-row form); else one wave per output cell.  The scaled-copy pass in front
+// of the streamed hidden layer always runs (it also writes feat_b, whichever conv path produced the features).
+enum ActRowsKernel { ACT_ROWS_NLR_1, ACT_ROWS_NLR_2, ACT_ROWS_GENERIC };
+static const char* const act_rows_kernel_name[] = {"k_nlr_fwd<1>", "k_nlr_fwd<2>", "k_nlr_generic"};
+struct ActRowsPlan {
+  ActRowsKernel kernel;
+  dim3 copy_grid, hgrid, zgrid;     // copy_grid.x == 0: no scaled-copy pass (the fallback reads eps_in in place)
+  unsigned block;
+};
+static ActRowsPlan plan_act_rows(const PlanIn& in, int n) {
+  const Layout& L = in.L;
+  ActRowsPlan p;
+  memset(&p, 0, sizeof(p));
+  if (!in.caps.fast_fc) {
+    p.kernel = ACT_ROWS_GENERIC; p.block = 256;
+    p.copy_grid = dim3(0, 1, 1);
+    p.hgrid = dim3((unsigned)rb_div_up((int64_t)n * 2 * L.H, 4));
+    p.zgrid = dim3((unsigned)rb_div_up((int64_t)n * L.NZ, 4));
+    return p;
+  }
+  const int mt = n <= 16 ? 1 : 2;
+  p.kernel = mt == 1 ? ACT_ROWS_NLR_1 : ACT_ROWS_NLR_2; p.block = 64 * RB_NL_FWD_WAVES;
+  const unsigned mch = (unsigned)rb_div_up(n, 16 * mt);
+  p.copy_grid = dim3((unsigned)rb_div_up((int64_t)n * L.F, 256));
+  p.hgrid = dim3((unsigned)(2 * rb_div_up(L.H, 16)), 1, mch);
+  p.zgrid = dim3((unsigned)(rb_div_up(L.Z, 16) + rb_div_up(L.NZ - L.Z, 16)), 1, mch);
+  return p;
+}
+
 // tiles of the weight-gradient problem of one noisy layer pair (which = 0: fc_z_v | fc_z_a, 1: fc_h_v | fc_h_a); ct > 0 selects the
 // pipelined body (M <= 32) with ct 256-column tiles per wave.  slots = sum-of-squares partials the launch writes.
 struct FcDwTiles { int dw_x, dw_y, slots; };

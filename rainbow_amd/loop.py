@@ -16,13 +16,17 @@ import torch
 from .evaluate import EpisodeTally, stream_quotas
 
 
-def train_device(agent, mem, env, args, T_max, on_eval=None):
+def train_device(agent, mem, env, args, T_max, on_eval=None, per_stream_noise=False):
     """main.py:146-184 for S = env.streams device streams (INTEGRATION.md §2): T counts environment steps, S per round;
     reset_noise once per replay_frequency env steps; from learn_start on, beta is annealed by priority_weight_increase * S per
     round, one learn() per replay_frequency env steps (learn_owed), target update and evaluation at `T % k < S`.
     on_eval(T), if given, is called at the evaluation rounds (args.evaluation_interval); it may synchronise.
+    per_stream_noise=True: every stream acts under its OWN noisy-net sample — agent.reset_noise_rows(S, rng=(args.seed, T)) at
+    the cadence of reset_noise() (which stays: learn() needs the learner's own sample) and act_batch(per_row_noise=True);
+    the default leaves today's launches exactly as they are (all S streams share the one online sample).
     Returns the number of learn() calls made."""
     S = env.streams
+    seed = int(getattr(args, "seed", 0))
     if S != mem.streams:
         raise ValueError("train_device: the environment has %d streams, the memory %d" % (S, mem.streams))
     increase = (1 - args.priority_weight) / (T_max - args.learn_start)           # main.py:123
@@ -35,10 +39,17 @@ def train_device(agent, mem, env, args, T_max, on_eval=None):
     if S == 1:
         states = states.unsqueeze(0)
     learn_owed, learns = 0.0, 0
+    if per_stream_noise:
+        agent.reset_noise_rows(S, rng=(seed, 0))                                  # S < replay_frequency: the first rounds come before the first redraw
     for T in range(1, T_max + 1, S):
         if T % args.replay_frequency < S:
             agent.reset_noise()                                                   # main.py:150-151
-        actions = agent.act_batch(states, device_out=True)                        # main.py:153, all streams, stays on the device
+            if per_stream_noise:
+                agent.reset_noise_rows(S, rng=(seed, T))
+        if per_stream_noise:
+            actions = agent.act_batch(states, device_out=True, per_row_noise=True)
+        else:
+            actions = agent.act_batch(states, device_out=True)                    # main.py:153, all streams, stays on the device
         next_states, rewards, nonterminals = env.step_device(actions)             # main.py:154 (ended streams: their reset stack)
         if clip_needed:
             rewards = rewards.clamp(-clip, clip)                                  # main.py:155-156
@@ -59,7 +70,7 @@ def train_device(agent, mem, env, args, T_max, on_eval=None):
     return learns
 
 
-def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None):
+def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None, per_stream_noise=False):
     """main.py:146-184 for S = len(emus) raw host emulators behind `front`, a rainbow_amd.frames.FrameStackVec (INTEGRATION.md
     §2).  emus[s] is duck-typed:
         reset(out_a)                 starts the next game — or, after a step that reported life_lost, does env.py:36-38's
@@ -76,8 +87,9 @@ def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None):
     stream's stack moves by one frame per round, so that frame is skipped.
     Cadences are train_device's: reset_noise once per replay_frequency env steps; from learn_start on, beta annealed by
     priority_weight_increase * S per round, one learn() per replay_frequency env steps (learn_owed), target update and on_eval
-    at `T % k < S`.  Returns the number of learn() calls made."""
+    at `T % k < S`.  per_stream_noise: as in train_device (one noise sample per emulator).  Returns the number of learn() calls made."""
     S = len(emus)
+    seed = int(getattr(args, "seed", 0))
     if S != mem.streams or S != front.streams:
         raise ValueError("train_host_vec: %d emulators, a front end of %d streams, a memory of %d" % (S, front.streams, mem.streams))
     increase = (1 - args.priority_weight) / (T_max - args.learn_start)           # main.py:123
@@ -90,10 +102,14 @@ def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None):
     states = front.reset_all()
     flags, rewards, terminals = np.zeros(S, dtype=np.uint8), np.zeros(S, dtype=np.float32), np.zeros(S, dtype=bool)
     learn_owed, learns = 0.0, 0
+    if per_stream_noise:
+        agent.reset_noise_rows(S, rng=(seed, 0))                                  # S < replay_frequency: the first rounds come before the first redraw
     for T in range(1, T_max + 1, S):
         if T % args.replay_frequency < S:
             agent.reset_noise()                                                   # main.py:150-151
-        actions = agent.act_batch(states)                                         # main.py:153, one forward for all streams
+            if per_stream_noise:
+                agent.reset_noise_rows(S, rng=(seed, T))
+        actions = agent.act_batch(states, per_row_noise=per_stream_noise)         # main.py:153, one forward for all streams
         scr = front.screens
         for s in range(S):
             f, r, done, life_lost = emus[s].step(int(actions[s]), scr[s, 0], scr[s, 1])    # main.py:154

@@ -9,7 +9,9 @@ Both sides launch the same Catch step kernel for their next frame stacks (A feed
 environment would upload whole frames instead, which A is not charged for), so the difference is the per-round synchronise,
 the D2H / by-value operand marshalling and the interpreter work around them.  Measured twice: the acting round alone, and the
 whole loop with reset_noise + learn at the reference's ratio (one learn per 4 env steps).  Blocks of rounds alternate
-A, B, A, B, ...; the figure is the median block.  Prints a small table and one JSON line.  Not the headline metric (bench.py is)."""
+A, B, A, B, ...; the figure is the median block.  Prints a small table and one JSON line.  Not the headline metric (bench.py is).
+
+  --per-stream-noise: instead, the device round against ITSELF with one noisy-net sample per stream (run_noise below)."""
 import json
 import os
 import statistics
@@ -102,11 +104,79 @@ def run(S, capacity, rounds, dev):
     return out
 
 
+def run_noise(S, capacity, rounds, dev):
+    """--per-stream-noise: the DEVICE round with the one shared noisy-net sample (A) against the same round with one sample per
+    stream (B: Agent.reset_noise_rows at train_device's cadence + act_batch(per_row_noise=True)), interleaved as above."""
+    from rainbow_amd import _lib as L
+    from rainbow_amd.agent import Agent
+    from rainbow_amd.envs import CatchVec
+    from rainbow_amd.memory import ReplayMemory
+    cfg = dict(bench.CONFIGS["pong-canonical-b32"])
+    args = bench.make_args(cfg, dev)
+    lib = L.load()
+    envs = {k: CatchVec(S, dev, seed=11) for k in "AB"}
+    agent = Agent(args, envs["A"])
+    mems = {k: ReplayMemory(args, capacity, seed=7, streams=S) for k in "AB"}
+    for m in mems.values():
+        vec_loop_bench.fill(m, lib, L, capacity, envs["A"].action_space(), seed=0)
+    st = {k: {"stacks": envs[k].reset().reshape(S, 4, 84, 84), "T": 1, "owed": 0.0} for k in "AB"}
+    agent.reset_noise_rows(S, rng=(0, 0))
+
+    def one_round(k, learn):
+        s = st[k]
+        rows = k == "B"
+        if rows and s["T"] % REPLAY_FREQUENCY < S:
+            agent.reset_noise_rows(S, rng=(0, s["T"]))
+        a = agent.act_batch(s["stacks"], device_out=True, per_row_noise=rows)
+        nxt, rw, nt = envs[k].step_device(a)
+        mems[k].append_streams(s["stacks"], a, rw, nonterminals=nt)
+        s["stacks"] = nxt
+        s["T"] += S
+        if learn:
+            s["owed"] += S / REPLAY_FREQUENCY
+            while s["owed"] >= 1.0:
+                agent.reset_noise()
+                agent.learn(mems[k])
+                s["owed"] -= 1.0
+
+    out = {}
+    for learn, tag in ((False, "act_round"), (True, "loop_round")):
+        for _ in range(20):
+            one_round("A", learn); one_round("B", learn)
+        ta, tb = [], []
+        for _ in range(BLOCKS):
+            ta.append(block(lambda: one_round("A", learn), rounds, dev))
+            tb.append(block(lambda: one_round("B", learn), rounds, dev))
+        out[tag + "_shared_us"], out[tag + "_per_stream_us"] = statistics.median(ta), statistics.median(tb)
+        out[tag + "_shared_spread_us"] = max(ta) - min(ta)
+        out[tag + "_per_stream_spread_us"] = max(tb) - min(tb)
+    for e in envs.values():
+        e.close()
+    return out
+
+
+def main_noise(dev, capacity):
+    result = {"capacity": capacity, "blocks": BLOCKS, "mode": "per-stream-noise"}
+    print("%3s | %-44s | %-44s" % ("S", "acting round us: shared / per-stream noise", "loop round us (+learns): shared / per-stream noise"))
+    for S in (1, 4, 16, 64):
+        rounds = max(40, 2000 // S)
+        r = {k: round(v, 2) for k, v in run_noise(S, capacity, rounds, dev).items()}
+        result["S%d" % S] = r
+        print("%3d | %10.1f / %-10.1f (spread %4.1f / %4.1f) | %10.1f / %-10.1f (spread %4.1f / %4.1f)"
+              % (S, r["act_round_shared_us"], r["act_round_per_stream_us"], r["act_round_shared_spread_us"], r["act_round_per_stream_spread_us"],
+                 r["loop_round_shared_us"], r["loop_round_per_stream_us"], r["loop_round_shared_spread_us"], r["loop_round_per_stream_spread_us"]),
+              flush=True)
+        torch.cuda.empty_cache()
+    print(json.dumps(result))
+
+
 def main():
     import __graft_entry__
     __graft_entry__.build()
     dev = torch.device("cuda", 0)
     capacity = int(os.environ.get("LOOP_CAPACITY", str(1 << 17)))      # a multiple of every S measured
+    if "--per-stream-noise" in sys.argv[1:]:
+        return main_noise(dev, capacity)
     result = {"capacity": capacity, "blocks": BLOCKS}
     print("%3s | %-34s | %-34s | env-steps/s host -> device" % ("S", "acting round us: host / device", "loop round us (+learns): host / device"))
     for S in (1, 4, 16, 64):
