@@ -352,9 +352,7 @@ class Agent:
         (no device-to-host copy): they are final after the stream synchronize below."""
         if self._noise_pending:
             self._flush_noise()
-        st = state
-        if st.dtype != torch.float32 or st.device != self.device or not st.is_contiguous():     # (env.py hands over exactly this)
-            st = state.to(device=self.device, dtype=torch.float32).contiguous()
+        st = self._f32_here(state)                    # (env.py hands over exactly this)
         pins = self._aq_ptrs
         # launch + wait in ONE C call: completion = the pinned action word changes (the head writes action and q as one 8-byte word);
         # the library polls it in a compiled loop (a Python loop over a numpy scalar sees the store a microsecond or two late),
@@ -398,29 +396,31 @@ class Agent:
                 L.check(self._lib, rc)
         self._noise_rows_drawn = rows
 
-    def _act_batch_rows(self, states, device_out, row0):
-        st = states
-        if st.dtype != torch.float32 or st.device != self.device or not st.is_contiguous():
-            st = states.to(device=self.device, dtype=torch.float32).contiguous()
+    def _f32_here(self, t):
+        """`t` as a contiguous float32 tensor on this agent's device (itself when it already is one)."""
+        if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+            t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        return t
+
+    def _run_chunked(self, st, device_out, cap, read_q, call):
+        """The batched act path over `st`, at most `cap` states per C call: call(state_ptr, m, lo, action_ptr, q_ptr) issues the
+        call for states [lo, lo + m) and returns its status.  device_out: the actions go straight into an int32 device tensor, q is
+        not asked for and nothing synchronises.  Otherwise both land in the pinned buffers, the stream is synchronised once per
+        chunk and the pinned actions (int64) or, with read_q, the pinned q (float32) are copied out."""
         n = int(st.shape[0])
-        if row0 < 0:
-            raise ValueError("act_batch: row0 must be >= 0, got %d" % row0)
-        if row0 + n > self._noise_rows_drawn:
-            raise ValueError("act_batch(per_row_noise=True): states %d .. %d need noise rows, reset_noise_rows drew %d"
-                             % (row0, row0 + n - 1, self._noise_rows_drawn))
-        cap = min(int(self._act_np.shape[0]), 256)
         acts = torch.empty(n, dtype=torch.int32, device=self.device) if device_out else None
-        out = None if device_out else np.empty(n, dtype=np.int64)
+        out = None if device_out else np.empty(n, dtype=np.float32 if read_q else np.int64)
         for lo in range(0, n, cap):
             m = min(cap, n - lo)
-            dst = acts[lo:lo + m].data_ptr() if device_out else self._act_pin.data_ptr()
-            rc = self._lib.rb_learner_act_batch_rows(self._h, st[lo:lo + m].data_ptr(), m, self._noise_rows[row0 + lo:row0 + lo + m].data_ptr(),
-                                                     dst, None if device_out else self._q_pin.data_ptr(), self._stream())
+            if device_out:
+                rc = call(st[lo:lo + m].data_ptr(), m, lo, acts[lo:lo + m].data_ptr(), None)
+            else:
+                rc = call(st[lo:lo + m].data_ptr(), m, lo, self._act_pin.data_ptr(), self._q_pin.data_ptr())
             if rc != 0:
                 L.check(self._lib, rc)
             if not device_out:
                 torch.cuda.current_stream(self.device).synchronize()
-                out[lo:lo + m] = self._act_np[:m]
+                out[lo:lo + m] = (self._q_np if read_q else self._act_np)[:m]
         return acts if device_out else out
 
     def act_batch(self, states, device_out=False, epsilon=None, rng=(0, 0), row0=0, per_row_noise=False):
@@ -439,57 +439,34 @@ class Agent:
         `epsilon`, or with fewer rows drawn than states passed, it raises ValueError."""
         if per_row_noise and epsilon is not None:
             raise ValueError("act_batch: per_row_noise and epsilon cannot be combined")
+        lib, h = self._lib, self._h
+        cap = int(self._act_np.shape[0])               # 2 * batch_size images fit the learner's activation buffers
         if per_row_noise and self.training:
-            return self._act_batch_rows(states, device_out, int(row0))
-        if epsilon is not None:
-            return self._act_batch_eps(states, device_out, float(epsilon), rng, int(row0))
-        self._flush_noise()
-        st = states
-        if st.dtype != torch.float32 or st.device != self.device or not st.is_contiguous():
-            st = states.to(device=self.device, dtype=torch.float32).contiguous()
-        n = int(st.shape[0])
-        cap = int(self._act_np.shape[0])          # 2 * batch_size images fit the learner's activation buffers
-        if device_out:
-            acts = torch.empty(n, dtype=torch.int32, device=self.device)
-            for lo in range(0, n, cap):
-                m = min(cap, n - lo)
-                rc = self._lib.rb_learner_act_batch(self._h, st[lo:lo + m].data_ptr(), m, 1 if self.training else 0,
-                                                    acts[lo:lo + m].data_ptr(), None, self._stream())
-                if rc != 0:
-                    L.check(self._lib, rc)
-            return acts
-        out = np.empty(n, dtype=np.int64)
-        for lo in range(0, n, cap):
-            m = min(cap, n - lo)
-            L.check(self._lib, self._lib.rb_learner_act_batch(self._h, st[lo:lo + m].data_ptr(), m,
-                                                              1 if self.training else 0, self._act_pin.data_ptr(),
-                                                              self._q_pin.data_ptr(), self._stream()))
-            torch.cuda.current_stream(self.device).synchronize()
-            out[lo:lo + m] = self._act_np[:m]
-        return out
+            row0 = int(row0)
+            st = self._f32_here(states)                # (no _flush_noise: the learner's own sample is not read)
+            n = int(st.shape[0])
+            if row0 < 0:
+                raise ValueError("act_batch: row0 must be >= 0, got %d" % row0)
+            if row0 + n > self._noise_rows_drawn:
+                raise ValueError("act_batch(per_row_noise=True): states %d .. %d need noise rows, reset_noise_rows drew %d"
+                                 % (row0, row0 + n - 1, self._noise_rows_drawn))
+            cap = min(cap, 256)
 
-    def _act_batch_eps(self, states, device_out, epsilon, rng, row0):
-        self._flush_noise()
-        st = states
-        if st.dtype != torch.float32 or st.device != self.device or not st.is_contiguous():
-            st = states.to(device=self.device, dtype=torch.float32).contiguous()
-        n = int(st.shape[0])
-        cap = int(self._act_np.shape[0])
-        noisy = 1 if self.training else 0
-        seed, rnd = int(rng[0]) & 0xFFFFFFFFFFFFFFFF, int(rng[1]) & 0xFFFFFFFFFFFFFFFF
-        acts = torch.empty(n, dtype=torch.int32, device=self.device) if device_out else None
-        out = None if device_out else np.empty(n, dtype=np.int64)
-        for lo in range(0, n, cap):
-            m = min(cap, n - lo)
-            dst = acts[lo:lo + m].data_ptr() if device_out else self._act_pin.data_ptr()
-            rc = self._lib.rb_learner_act_batch_eps(self._h, st[lo:lo + m].data_ptr(), m, noisy, epsilon, seed, rnd, row0 + lo, dst,
-                                                    None if device_out else self._q_pin.data_ptr(), None, self._stream())
-            if rc != 0:
-                L.check(self._lib, rc)
-            if not device_out:
-                torch.cuda.current_stream(self.device).synchronize()
-                out[lo:lo + m] = self._act_np[:m]
-        return acts if device_out else out
+            def call(sp, m, lo, ap, qp):
+                return lib.rb_learner_act_batch_rows(h, sp, m, self._noise_rows[row0 + lo:row0 + lo + m].data_ptr(), ap, qp, self._stream())
+        else:
+            if epsilon is not None:
+                epsilon, row0 = float(epsilon), int(row0)
+                seed, rnd = int(rng[0]) & 0xFFFFFFFFFFFFFFFF, int(rng[1]) & 0xFFFFFFFFFFFFFFFF
+            self._flush_noise()
+            st = self._f32_here(states)
+            noisy = 1 if self.training else 0
+
+            def call(sp, m, lo, ap, qp):
+                if epsilon is None:
+                    return lib.rb_learner_act_batch(h, sp, m, noisy, ap, qp, self._stream())
+                return lib.rb_learner_act_batch_eps(h, sp, m, noisy, epsilon, seed, rnd, row0 + lo, ap, qp, None, self._stream())
+        return self._run_chunked(st, device_out, cap, False, call)
 
     def act_e_greedy(self, state, epsilon=0.001):
         """agent.py:58-59."""
@@ -505,22 +482,16 @@ class Agent:
         [self.evaluate_q(s) for s in states] as ONE forward per `chunk` states (6 launches for a 500-state validation
         memory, test.py:38-39, instead of 500 single-state launch chains with a stream sync each)."""
         self._flush_noise()
-        st = states.to(device=self.device, dtype=torch.float32).contiguous()
-        n = int(st.shape[0])
-        out = np.empty(n, dtype=np.float32)
+        st = self._f32_here(states)
+        noisy = 1 if self.training else 0
         chunk = max(1, min(int(chunk), 4096))
-        if self._q_pin.numel() < min(n, chunk):
-            self._act_pin = torch.zeros(min(n, chunk), dtype=torch.int32).pin_memory()
-            self._q_pin = torch.zeros(min(n, chunk), dtype=torch.float32).pin_memory()
+        need = min(int(st.shape[0]), chunk)
+        if self._q_pin.numel() < need:
+            self._act_pin = torch.zeros(need, dtype=torch.int32).pin_memory()
+            self._q_pin = torch.zeros(need, dtype=torch.float32).pin_memory()
             self._act_np, self._q_np = self._act_pin.numpy(), self._q_pin.numpy()
-        for lo in range(0, n, chunk):
-            m = min(chunk, n - lo)
-            L.check(self._lib, self._lib.rb_learner_act_batch(self._h, st[lo:lo + m].data_ptr(), m,
-                                                              1 if self.training else 0, self._act_pin.data_ptr(),
-                                                              self._q_pin.data_ptr(), self._stream()))
-            torch.cuda.current_stream(self.device).synchronize()
-            out[lo:lo + m] = self._q_np[:m]
-        return out
+        return self._run_chunked(st, False, chunk, True,
+                                 lambda sp, m, lo, ap, qp: self._lib.rb_learner_act_batch(self._h, sp, m, noisy, ap, qp, self._stream()))
 
     def evaluate_q_memory(self, val_mem, chunk=512):
         """test.py:38-39 in one call: Q of every state the reference's `for state in val_mem` visits — ALL `capacity` slots

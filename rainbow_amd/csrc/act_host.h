@@ -1,5 +1,6 @@
-// act_host.h — host side of Agent.act / evaluate_q: the one-launch act path (act_path.h) and the batched forward.
-// Included by learner.hip only, after fc_dispatch.h (forward, nl_h / nl_z) and head.h (k_head_act).
+// act_host.h — host side of Agent.act / evaluate_q: the one-launch act path (act_path.h) and the batched forward + head
+// (act_batch_run, behind the three rb_learner_act_batch* entry points).
+// Included by learner.hip only, after fc_dispatch.h (forward, fc_rows_fwd, nl_h / nl_z) and head.h (k_head_act, k_head_act_eps).
 #pragma once
 #include "learner_internal.h"
 
@@ -142,54 +143,32 @@ int rb_learner_act_wait(rb_learner_t* l, const float* state_dev, int32_t noisy, 
 
 }  // extern "C"
 
+// (re)allocate one f32 buffer of `count` floats; `who` names the entry point in the message
+static int regrow_f32(float** p, int64_t count, const char* who) {
+  if (*p) rb_dev_free(*p);
+  *p = nullptr;
+  hipError_t e = rb_dev_malloc((void**)p, (size_t)count * 4);
+  if (e != hipSuccess) { rb_set_error("%s: hipMalloc(%lld B) failed: %s", who, (long long)count * 4, hipGetErrorString(e)); return RB_ERR_OOM; }
+  return RB_OK;
+}
+
 // The forward buffers are sized for the learn step's 3B images; batched evaluation (test.py:38-39 over a 500-state
 // validation memory) may ask for more rows: grow them (synchronising; happens once per size).
 static int ensure_rows(rb_learner* l, int rows) {
   if (rows <= l->rows_cap) return RB_OK;
   const Layout& L = l->L;
   RB_HIP_TRY(hipDeviceSynchronize());
-  auto regrow = [&](float** p, int64_t count) -> int {
-    if (*p) rb_dev_free(*p);
-    *p = nullptr;
-    hipError_t e = rb_dev_malloc((void**)p, (size_t)count * 4);
-    if (e != hipSuccess) { rb_set_error("rb_learner_act_batch: hipMalloc(%lld B) failed: %s", (long long)count * 4, hipGetErrorString(e)); return RB_ERR_OOM; }
-    return RB_OK;
-  };
+  const char* who = "rb_learner_act_batch";
   int rc;
   for (int i = 0; i < L.nconv; ++i)
-    if ((rc = regrow(&l->act[i], (int64_t)rows * L.conv[i].cout * L.conv[i].P())) != RB_OK) return rc;
-  if ((rc = regrow(&l->hpart, (int64_t)l->caps.hs * rows * 2 * L.H)) != RB_OK) return rc;
-  if ((rc = regrow(&l->h, (int64_t)rows * 2 * L.H)) != RB_OK) return rc;
-  if ((rc = regrow(&l->feat_b, (int64_t)rows * (L.F + 16))) != RB_OK) return rc;
-  if ((rc = regrow(&l->h_b, (int64_t)rows * (2 * L.H + 16))) != RB_OK) return rc;
-  if ((rc = regrow(&l->logits, (int64_t)rows * L.NZ)) != RB_OK) return rc;
+    if ((rc = regrow_f32(&l->act[i], (int64_t)rows * L.conv[i].cout * L.conv[i].P(), who)) != RB_OK) return rc;
+  if ((rc = regrow_f32(&l->hpart, (int64_t)l->caps.hs * rows * 2 * L.H, who)) != RB_OK) return rc;
+  if ((rc = regrow_f32(&l->h, (int64_t)rows * 2 * L.H, who)) != RB_OK) return rc;
+  if ((rc = regrow_f32(&l->feat_b, (int64_t)rows * (L.F + 16), who)) != RB_OK) return rc;
+  if ((rc = regrow_f32(&l->h_b, (int64_t)rows * (2 * L.H + 16), who)) != RB_OK) return rc;
+  if ((rc = regrow_f32(&l->logits, (int64_t)rows * L.NZ, who)) != RB_OK) return rc;
   RB_HIP_TRY(hipMemset(l->hpart, 0, (size_t)l->caps.hs * rows * 2 * L.H * 4));
   l->rows_cap = rows;
-  return RB_OK;
-}
-
-extern "C" {
-
-int rb_learner_act_batch(rb_learner_t* l, const float* states_dev, int32_t n, int32_t noisy, int32_t* actions_dev,
-                         float* q_dev, rb_stream_t stream) {
-  RB_REQUIRE(l && states_dev, "rb_learner_act_batch: NULL argument");
-  RB_FLUSH_UPDATE(l, stream);
-  const Layout& L = l->L;
-  RB_REQUIRE(n >= 1 && n <= 4096, "rb_learner_act_batch: n must be in [1, 4096]");
-  {
-    int rc0 = ensure_rows(l, n);
-    if (rc0 != RB_OK) return rc0;
-  }
-  if (n == 1) return rb_learner_act(l, states_dev, noisy, actions_dev, q_dev, stream);
-  ImgSrc src;
-  memset(&src, 0, sizeof(src));
-  src.f32 = states_dev; src.B = n;
-  const NetPtrs on = net_ptrs(L, l->p_online, noisy ? l->n_online : l->zero_noise);
-  int rc = forward(l, n, 0, src, on, on, (hipStream_t)stream);     // the training kernels: n images share every weight read
-  if (rc != RB_OK) return rc;
-  RB_LAUNCH(k_head_act, dim3((unsigned)n), dim3(256), stream, L.Z, L.A, (const float*)l->logits, 0, (const float*)l->support,
-            actions_dev, q_dev);
-  RB_LAUNCH_CHECK();
   return RB_OK;
 }
 
@@ -198,97 +177,85 @@ static int ensure_rows_scaled(rb_learner* l, int rows) {
   if (rows <= l->rows_s_cap) return RB_OK;
   const Layout& L = l->L;
   if (l->feat_s || l->h_s) RB_HIP_TRY(hipDeviceSynchronize());   // (a launch in flight may still read what is freed below)
-  float** bufs[2] = {&l->feat_s, &l->h_s};
-  const int64_t counts[2] = {(int64_t)rows * (2 * L.F + 16), (int64_t)rows * (2 * L.H + 16)};
-  for (int i = 0; i < 2; ++i) {
-    if (*bufs[i]) rb_dev_free(*bufs[i]);
-    *bufs[i] = nullptr;
-    hipError_t e = rb_dev_malloc((void**)bufs[i], (size_t)counts[i] * 4);
-    if (e != hipSuccess) {
-      l->rows_s_cap = 0;
-      rb_set_error("rb_learner_act_batch_rows: hipMalloc(%lld B) failed: %s", (long long)counts[i] * 4, hipGetErrorString(e));
-      return RB_ERR_OOM;
-    }
-  }
+  l->rows_s_cap = 0;
+  int rc;
+  if ((rc = regrow_f32(&l->feat_s, (int64_t)rows * (2 * L.F + 16), "rb_learner_act_batch_rows")) != RB_OK) return rc;
+  if ((rc = regrow_f32(&l->h_s, (int64_t)rows * (2 * L.H + 16), "rb_learner_act_batch_rows")) != RB_OK) return rc;
   l->rows_s_cap = rows;
   return RB_OK;
 }
 
-// rb_learner_act_batch with row i's noisy layers under noise row i (include/rainbow_hip.h; noisy_rows.h has the arithmetic)
+// One batched forward + head: what the three rb_learner_act_batch* entry points below ask for, after their own argument checks.
+struct ActBatchReq {
+  const float* states;        // f32 [n][history][84][84]
+  int n, noisy;
+  const float* noise_rows;    // non-NULL: row i's noisy layers run under noise row i (fc_rows_fwd); `noisy` is not read
+  bool eps;                   // the e-greedy draw in the head (k_head_act_eps) with the five values below
+  float epsilon;
+  uint64_t rng_seed, rng_round;
+  int row0;
+  uint8_t* explored;
+  int32_t* actions;
+  float* q;
+};
+static int act_batch_run(rb_learner* l, const ActBatchReq& r, hipStream_t stream) {
+  RB_FLUSH_UPDATE(l, stream);
+  const Layout& L = l->L;
+  const int n = r.n;
+  int rc = ensure_rows(l, n);
+  if (rc != RB_OK) return rc;
+  ImgSrc src;
+  memset(&src, 0, sizeof(src));
+  src.f32 = r.states; src.B = n;
+  if (r.noise_rows) {
+    const ActRowsPlan p = plan_act_rows(plan_in(l), n);
+    if (p.kernel != ACT_ROWS_GENERIC && (rc = ensure_rows_scaled(l, n)) != RB_OK) return rc;
+    const NetPtrs on = net_ptrs(L, l->p_online, l->zero_noise);     // (the conv layers carry no noise)
+    for (int layer = 0; layer < L.nconv; ++layer)
+      if ((rc = conv_fwd(l, layer, n, 0, src, on, on, stream)) != RB_OK) return rc;
+    rc = fc_rows_fwd(l, p, n, r.noise_rows, on, stream);
+  } else {
+    const NetPtrs on = net_ptrs(L, l->p_online, r.noisy ? l->n_online : l->zero_noise);
+    rc = forward(l, n, 0, src, on, on, stream);                     // the training kernels: n images share every weight read
+  }
+  if (rc != RB_OK) return rc;
+  if (r.eps) {
+    RB_LAUNCH(k_head_act_eps, dim3((unsigned)n), dim3(256), stream, L.Z, L.A, (const float*)l->logits, (const float*)l->support, r.epsilon,
+              r.rng_seed, r.rng_round, r.row0, r.actions, r.q, r.explored);
+  } else {
+    RB_LAUNCH(k_head_act, dim3((unsigned)n), dim3(256), stream, L.Z, L.A, (const float*)l->logits, 0, (const float*)l->support,
+              r.actions, r.q);
+  }
+  RB_LAUNCH_CHECK();
+  return RB_OK;
+}
+
+extern "C" {
+
+int rb_learner_act_batch(rb_learner_t* l, const float* states_dev, int32_t n, int32_t noisy, int32_t* actions_dev,
+                         float* q_dev, rb_stream_t stream) {
+  RB_REQUIRE(l && states_dev, "rb_learner_act_batch: NULL argument");
+  RB_FLUSH_UPDATE(l, stream);     // (this entry has always flushed before its range check; act_batch_run then finds nothing pending)
+  RB_REQUIRE(n >= 1 && n <= 4096, "rb_learner_act_batch: n must be in [1, 4096]");
+  if (n == 1) return rb_learner_act(l, states_dev, noisy, actions_dev, q_dev, stream);      // the one-launch path
+  ActBatchReq r;
+  memset(&r, 0, sizeof(r));
+  r.states = states_dev; r.n = n; r.noisy = noisy; r.actions = actions_dev; r.q = q_dev;
+  return act_batch_run(l, r, (hipStream_t)stream);
+}
+
+// rb_learner_act_batch with row i's noisy layers under noise row i (include/rainbow_hip.h; noisy_rows.h has the arithmetic);
+// n == 1 runs the rows forward as well
 int rb_learner_act_batch_rows(rb_learner_t* l, const float* states_dev, int32_t n, const float* noise_rows_dev, int32_t* actions_dev,
                               float* q_dev, rb_stream_t stream) {
   RB_REQUIRE(l != nullptr, "rb_learner_act_batch_rows: NULL handle (l)");
   RB_REQUIRE(states_dev != nullptr, "rb_learner_act_batch_rows: NULL states_dev");
   RB_REQUIRE(noise_rows_dev != nullptr, "rb_learner_act_batch_rows: NULL noise_rows_dev");
   RB_REQUIRE(n >= 1 && n <= 256, "rb_learner_act_batch_rows: n must be in [1, 256], got %d", (int)n);
-  RB_FLUSH_UPDATE(l, stream);
-  const Layout& L = l->L;
-  {
-    int rc0 = ensure_rows(l, n);
-    if (rc0 != RB_OK) return rc0;
-  }
-  const ActRowsPlan p = plan_act_rows(plan_in(l), n);
-  if (p.kernel != ACT_ROWS_GENERIC) {
-    int rc0 = ensure_rows_scaled(l, n);
-    if (rc0 != RB_OK) return rc0;
-  }
-  ImgSrc src;
-  memset(&src, 0, sizeof(src));
-  src.f32 = states_dev; src.B = n;
-  const NetPtrs on = net_ptrs(L, l->p_online, l->zero_noise);     // (the conv layers carry no noise)
-  for (int layer = 0; layer < L.nconv; ++layer) {
-    int rc = conv_fwd(l, layer, n, 0, src, on, on, (hipStream_t)stream);
-    if (rc != RB_OK) return rc;
-  }
-  const float* feat = l->act[L.nconv - 1];
-  const int nn = (int)L.n_noise;
-  if (p.kernel == ACT_ROWS_GENERIC) {
-    NlRowsGenericArgs h;
-    h.x = feat; h.ldx = L.F; h.mu = on.h_mu; h.sigma = on.h_sigma; h.bmu = on.h_bmu; h.bsigma = on.h_bsigma;
-    h.noise_rows = noise_rows_dev; h.n_noise = nn; h.ein_off = (int)L.h_ein; h.eout_off = (int)L.h_eout;
-    h.M = n; h.N = 2 * L.H; h.K = L.F; h.split_row = L.H; h.x_off1 = 0; h.ein_off1 = L.F;
-    h.out = l->h; h.ld_out = 2 * L.H; h.relu = 1;
-    RB_LAUNCH_T("fc_h_rows:k_nlr_generic", k_nlr_generic, p.hgrid, dim3(p.block), stream, h);
-    RB_LAUNCH_CHECK();
-    NlRowsGenericArgs z;
-    z.x = l->h; z.ldx = 2 * L.H; z.mu = on.z_mu; z.sigma = on.z_sigma; z.bmu = on.z_bmu; z.bsigma = on.z_bsigma;
-    z.noise_rows = noise_rows_dev; z.n_noise = nn; z.ein_off = (int)L.z_ein; z.eout_off = (int)L.z_eout;
-    z.M = n; z.N = L.NZ; z.K = L.H; z.split_row = L.Z; z.x_off1 = L.H; z.ein_off1 = L.H;
-    z.out = l->logits; z.ld_out = L.NZ; z.relu = 0;
-    RB_LAUNCH_T("fc_z_rows:k_nlr_generic", k_nlr_generic, p.zgrid, dim3(p.block), stream, z);
-    RB_LAUNCH_CHECK();
-  } else {
-    RB_LAUNCH(k_block_copy_rows, p.copy_grid, dim3(256), stream, feat, (int)n, L.F, noise_rows_dev, nn, (int)L.h_ein, l->feat_b, l->feat_s);
-    RB_LAUNCH_CHECK();
-    NlRowsArgs h;
-    h.x = l->feat_b; h.xs = l->feat_s; h.mu = on.h_mu; h.sigma = on.h_sigma; h.bmu = on.h_bmu; h.bsigma = on.h_bsigma;
-    h.noise_rows = noise_rows_dev; h.n_noise = nn; h.eout_off = (int)L.h_eout;
-    h.M = n; h.K = L.F; h.n_groups = 2;
-    h.grp[0] = NlRowGroup{0, L.H, 0, 0, 0};
-    h.grp[1] = NlRowGroup{L.H, L.H, 0, L.F, (int)rb_div_up(L.H, 16)};
-    h.out = l->h; h.out_blocked = l->h_b; h.out_scaled = l->h_s; h.next_ein_off = (int)L.z_ein; h.ld_out = 2 * L.H; h.relu = 1;
-    NlRowsArgs z;
-    z.x = l->h_b; z.xs = l->h_s; z.mu = on.z_mu; z.sigma = on.z_sigma; z.bmu = on.z_bmu; z.bsigma = on.z_bsigma;
-    z.noise_rows = noise_rows_dev; z.n_noise = nn; z.eout_off = (int)L.z_eout;
-    z.M = n; z.K = L.H; z.n_groups = 2;
-    z.grp[0] = NlRowGroup{0, L.Z, 0, 0, 0};
-    z.grp[1] = NlRowGroup{L.Z, L.NZ - L.Z, L.H, L.H, (int)rb_div_up(L.Z, 16)};
-    z.out = l->logits; z.out_blocked = nullptr; z.out_scaled = nullptr; z.next_ein_off = 0; z.ld_out = L.NZ; z.relu = 0;
-    if (p.kernel == ACT_ROWS_NLR_1) {
-      RB_LAUNCH_T("fc_h_rows:k_nlr_fwd", k_nlr_fwd<1>, p.hgrid, dim3(p.block), stream, h);
-      RB_LAUNCH_CHECK();
-      RB_LAUNCH_T("fc_z_rows:k_nlr_fwd", k_nlr_fwd<1>, p.zgrid, dim3(p.block), stream, z);
-    } else {
-      RB_LAUNCH_T("fc_h_rows:k_nlr_fwd", k_nlr_fwd<2>, p.hgrid, dim3(p.block), stream, h);
-      RB_LAUNCH_CHECK();
-      RB_LAUNCH_T("fc_z_rows:k_nlr_fwd", k_nlr_fwd<2>, p.zgrid, dim3(p.block), stream, z);
-    }
-    RB_LAUNCH_CHECK();
-  }
-  RB_LAUNCH(k_head_act, dim3((unsigned)n), dim3(256), stream, L.Z, L.A, (const float*)l->logits, 0, (const float*)l->support,
-            actions_dev, q_dev);
-  RB_LAUNCH_CHECK();
-  return RB_OK;
+  ActBatchReq r;
+  memset(&r, 0, sizeof(r));
+  r.states = states_dev; r.n = n; r.noise_rows = noise_rows_dev; r.actions = actions_dev; r.q = q_dev;
+  return act_batch_run(l, r, (hipStream_t)stream);
 }
 
 // rb_learner_act_batch with the e-greedy draw in the head (include/rainbow_hip.h): the same forward, the same buffers.
@@ -300,30 +267,19 @@ int rb_learner_act_batch_eps(rb_learner_t* l, const float* states_dev, int32_t n
   RB_REQUIRE(epsilon >= 0.0f, "rb_learner_act_batch_eps: epsilon must be a number >= 0, got %g", (double)epsilon);
   RB_REQUIRE(row0 >= 0, "rb_learner_act_batch_eps: row0 must be >= 0, got %d", (int)row0);
   RB_REQUIRE(n >= 1 && n <= 4096, "rb_learner_act_batch_eps: n must be in [1, 4096]");
-  const Layout& L = l->L;
   if (n == 1) {
     // the one-launch act path, then one wave that applies the draw of row0 to the action it stored
     const int rc1 = rb_learner_act_batch(l, states_dev, 1, noisy, actions_dev, q_dev, stream);
     if (rc1 != RB_OK) return rc1;
-    RB_LAUNCH(k_act_eps_override, dim3(1), dim3(64), stream, L.A, epsilon, rng_seed, rng_round, (int)row0, actions_dev, explored_dev);
+    RB_LAUNCH(k_act_eps_override, dim3(1), dim3(64), stream, l->L.A, epsilon, rng_seed, rng_round, (int)row0, actions_dev, explored_dev);
     RB_LAUNCH_CHECK();
     return RB_OK;
   }
-  RB_FLUSH_UPDATE(l, stream);
-  {
-    int rc0 = ensure_rows(l, n);
-    if (rc0 != RB_OK) return rc0;
-  }
-  ImgSrc src;
-  memset(&src, 0, sizeof(src));
-  src.f32 = states_dev; src.B = n;
-  const NetPtrs on = net_ptrs(L, l->p_online, noisy ? l->n_online : l->zero_noise);
-  int rc = forward(l, n, 0, src, on, on, (hipStream_t)stream);
-  if (rc != RB_OK) return rc;
-  RB_LAUNCH(k_head_act_eps, dim3((unsigned)n), dim3(256), stream, L.Z, L.A, (const float*)l->logits, (const float*)l->support, epsilon,
-            rng_seed, rng_round, (int)row0, actions_dev, q_dev, explored_dev);
-  RB_LAUNCH_CHECK();
-  return RB_OK;
+  ActBatchReq r;
+  memset(&r, 0, sizeof(r));
+  r.states = states_dev; r.n = n; r.noisy = noisy; r.actions = actions_dev; r.q = q_dev;
+  r.eps = true; r.epsilon = epsilon; r.rng_seed = rng_seed; r.rng_round = rng_round; r.row0 = row0; r.explored = explored_dev;
+  return act_batch_run(l, r, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // fc_dispatch.h — the noisy-linear launches of the learner, forward and backward: take the plan (learner_plan.h), fill the argument
-// structs, switch on the kernel id.  Included by learner.hip only, after conv_dispatch.h (plan_in) and grad_finish.h (the kernels of
-// the small passes).
+// structs, switch on the kernel id.  Included by learner.hip only, after conv_dispatch.h (plan_in), grad_finish.h (the kernels of
+// the small passes) and noisy_rows.h (the per-row-noise kernels of fc_rows_fwd).
 #pragma once
 #include "learner_plan.h"
 
@@ -95,6 +95,68 @@ static int forward(rb_learner* l, int n_on, int n_tg, const ImgSrc& src, const N
     if (rc != RB_OK) return rc;
   }
   return fc_forward(l, n_on, n_tg, on, tg, stream);
+}
+
+// Arguments of one per-row-noise layer (noisy_rows.h) over n rows, which = 0: fc_z_v | fc_z_a, 1: fc_h_v | fc_h_a — for the streamed
+// kernel (k-blocked operands, the hidden layer's epilogue writes the output layer's) and for the one-wave-per-cell fallback.
+static NlRowsArgs nl_rows_args(rb_learner* l, const NetPtrs& on, int which, int n, const float* noise_rows) {
+  const Layout& L = l->L;
+  const NlWeights w = which ? nl_h(on) : nl_z(on);
+  const int rows0 = which ? L.H : L.Z;             // weight rows of the value stream; the advantage stream's follow
+  NlRowsArgs a;
+  a.x = which ? l->feat_b : l->h_b; a.xs = which ? l->feat_s : l->h_s;
+  a.mu = w.mu; a.sigma = w.sigma; a.bmu = w.bmu; a.bsigma = w.bsigma;
+  a.noise_rows = noise_rows; a.n_noise = (int)L.n_noise; a.eout_off = (int)(which ? L.h_eout : L.z_eout);
+  a.M = n; a.K = which ? L.F : L.H; a.n_groups = 2;
+  a.grp[0] = NlRowGroup{0, rows0, 0, 0, 0};
+  a.grp[1] = NlRowGroup{rows0, which ? L.H : L.NZ - L.Z, which ? 0 : L.H, a.K, (int)rb_div_up(rows0, 16)};
+  a.out = which ? l->h : l->logits; a.out_blocked = which ? l->h_b : nullptr; a.out_scaled = which ? l->h_s : nullptr;
+  a.next_ein_off = which ? (int)L.z_ein : 0; a.ld_out = which ? 2 * L.H : L.NZ; a.relu = which;
+  return a;
+}
+static NlRowsGenericArgs nl_rows_generic_args(rb_learner* l, const NetPtrs& on, int which, int n, const float* noise_rows) {
+  const Layout& L = l->L;
+  const NlWeights w = which ? nl_h(on) : nl_z(on);
+  NlRowsGenericArgs a;
+  a.x = which ? l->act[L.nconv - 1] : l->h; a.ldx = which ? L.F : 2 * L.H;
+  a.mu = w.mu; a.sigma = w.sigma; a.bmu = w.bmu; a.bsigma = w.bsigma;
+  a.noise_rows = noise_rows; a.n_noise = (int)L.n_noise;
+  a.ein_off = (int)(which ? L.h_ein : L.z_ein); a.eout_off = (int)(which ? L.h_eout : L.z_eout);
+  a.M = n; a.N = which ? 2 * L.H : L.NZ; a.K = which ? L.F : L.H;
+  a.split_row = which ? L.H : L.Z; a.x_off1 = which ? 0 : L.H; a.ein_off1 = a.K;
+  a.out = which ? l->h : l->logits; a.ld_out = a.N; a.relu = which;
+  return a;
+}
+
+// Hidden and output layer of n online images with row i under noise row i (rb_learner_act_batch_rows): features to the logits.
+static int fc_rows_fwd(rb_learner* l, const ActRowsPlan& p, int n, const float* noise_rows, const NetPtrs& on, hipStream_t stream) {
+  const Layout& L = l->L;
+  if (p.kernel == ACT_ROWS_GENERIC) {
+    const NlRowsGenericArgs h = nl_rows_generic_args(l, on, 1, n, noise_rows), z = nl_rows_generic_args(l, on, 0, n, noise_rows);
+    RB_LAUNCH_T("fc_h_rows:k_nlr_generic", k_nlr_generic, p.hgrid, dim3(p.block), stream, h);
+    RB_LAUNCH_CHECK();
+    RB_LAUNCH_T("fc_z_rows:k_nlr_generic", k_nlr_generic, p.zgrid, dim3(p.block), stream, z);
+    RB_LAUNCH_CHECK();
+    return RB_OK;
+  }
+  RB_LAUNCH(k_block_copy_rows, p.copy_grid, dim3(256), stream, (const float*)l->act[L.nconv - 1], n, L.F, noise_rows, (int)L.n_noise,
+            (int)L.h_ein, l->feat_b, l->feat_s);
+  RB_LAUNCH_CHECK();
+  const NlRowsArgs h = nl_rows_args(l, on, 1, n, noise_rows), z = nl_rows_args(l, on, 0, n, noise_rows);
+  switch (p.kernel) {
+    case ACT_ROWS_NLR_1:
+      RB_LAUNCH_T("fc_h_rows:k_nlr_fwd", k_nlr_fwd<1>, p.hgrid, dim3(p.block), stream, h);
+      RB_LAUNCH_CHECK();
+      RB_LAUNCH_T("fc_z_rows:k_nlr_fwd", k_nlr_fwd<1>, p.zgrid, dim3(p.block), stream, z);
+      break;
+    default:
+      RB_LAUNCH_T("fc_h_rows:k_nlr_fwd", k_nlr_fwd<2>, p.hgrid, dim3(p.block), stream, h);
+      RB_LAUNCH_CHECK();
+      RB_LAUNCH_T("fc_z_rows:k_nlr_fwd", k_nlr_fwd<2>, p.zgrid, dim3(p.block), stream, z);
+      break;
+  }
+  RB_LAUNCH_CHECK();
+  return RB_OK;
 }
 
 // Arguments of the weight-gradient problem of one noisy layer pair (which = 0: fc_z_v | fc_z_a, 1: fc_h_v | fc_h_a) over M

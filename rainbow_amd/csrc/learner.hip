@@ -26,10 +26,10 @@
 #include "grad_finish.h"
 #include "head.h"
 #include "adam_kernels.h"
+#include "noisy_rows.h"
 #include "conv_dispatch.h"
 #include "fc_dispatch.h"
 #include "optimizer_host.h"
-#include "noisy_rows.h"
 #include "act_host.h"
 #include "exchange_host.h"
 #include "layout_api.h"

@@ -10,34 +10,20 @@ their u8 screens into the front end's pinned staging, one upload and one launch 
 
 `evaluate_vec` / `evaluate_host_vec` are the reference's evaluation (test.py:13-41) for the same two kinds of environment:
 epsilon-greedy actions drawn in the batched act path, the per-episode list of returns, `episodes` spread evenly over the streams."""
+from contextlib import contextmanager
+
 import numpy as np
 import torch
 
 from .evaluate import EpisodeTally, stream_quotas
 
 
-def train_device(agent, mem, env, args, T_max, on_eval=None, per_stream_noise=False):
-    """main.py:146-184 for S = env.streams device streams (INTEGRATION.md §2): T counts environment steps, S per round;
-    reset_noise once per replay_frequency env steps; from learn_start on, beta is annealed by priority_weight_increase * S per
-    round, one learn() per replay_frequency env steps (learn_owed), target update and evaluation at `T % k < S`.
-    on_eval(T), if given, is called at the evaluation rounds (args.evaluation_interval); it may synchronise.
-    per_stream_noise=True: every stream acts under its OWN noisy-net sample — agent.reset_noise_rows(S, rng=(args.seed, T)) at
-    the cadence of reset_noise() (which stays: learn() needs the learner's own sample) and act_batch(per_row_noise=True);
-    the default leaves today's launches exactly as they are (all S streams share the one online sample).
-    Returns the number of learn() calls made."""
-    S = env.streams
+def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states, round_fn):
+    """The cadence of main.py:146-184 at S environment steps per round, shared by train_device and train_host_vec:
+    round_fn(states) acts, steps the environment and appends the round to `mem`, and returns the next states."""
     seed = int(getattr(args, "seed", 0))
-    if S != mem.streams:
-        raise ValueError("train_device: the environment has %d streams, the memory %d" % (S, mem.streams))
     increase = (1 - args.priority_weight) / (T_max - args.learn_start)           # main.py:123
-    clip = float(getattr(args, "reward_clip", 0) or 0)
-    lo, hi = getattr(env, "reward_range", (-float("inf"), float("inf")))
-    clip_needed = clip > 0 and (lo < -clip or hi > clip)
     eval_every = int(getattr(args, "evaluation_interval", 0) or 0)
-    agent.train()
-    states = env.reset()
-    if S == 1:
-        states = states.unsqueeze(0)
     learn_owed, learns = 0.0, 0
     if per_stream_noise:
         agent.reset_noise_rows(S, rng=(seed, 0))                                  # S < replay_frequency: the first rounds come before the first redraw
@@ -46,14 +32,7 @@ def train_device(agent, mem, env, args, T_max, on_eval=None, per_stream_noise=Fa
             agent.reset_noise()                                                   # main.py:150-151
             if per_stream_noise:
                 agent.reset_noise_rows(S, rng=(seed, T))
-        if per_stream_noise:
-            actions = agent.act_batch(states, device_out=True, per_row_noise=True)
-        else:
-            actions = agent.act_batch(states, device_out=True)                    # main.py:153, all streams, stays on the device
-        next_states, rewards, nonterminals = env.step_device(actions)             # main.py:154 (ended streams: their reset stack)
-        if clip_needed:
-            rewards = rewards.clamp(-clip, clip)                                  # main.py:155-156
-        mem.append_streams(states, actions, rewards, nonterminals=nonterminals)   # main.py:157
+        states = round_fn(states)                                                 # main.py:153-157
         if T >= args.learn_start:
             mem.priority_weight = min(mem.priority_weight + increase * S, 1)      # main.py:161
             learn_owed += S / args.replay_frequency
@@ -66,8 +45,39 @@ def train_device(agent, mem, env, args, T_max, on_eval=None, per_stream_noise=Fa
                 agent.train()
             if T % args.target_update < S:
                 agent.update_target_net()                                         # main.py:177-178
-        states = next_states
     return learns
+
+
+def train_device(agent, mem, env, args, T_max, on_eval=None, per_stream_noise=False):
+    """main.py:146-184 for S = env.streams device streams (INTEGRATION.md §2): T counts environment steps, S per round;
+    reset_noise once per replay_frequency env steps; from learn_start on, beta is annealed by priority_weight_increase * S per
+    round, one learn() per replay_frequency env steps (learn_owed), target update and evaluation at `T % k < S`.
+    on_eval(T), if given, is called at the evaluation rounds (args.evaluation_interval); it may synchronise.
+    per_stream_noise=True: every stream acts under its OWN noisy-net sample — agent.reset_noise_rows(S, rng=(args.seed, T)) at
+    the cadence of reset_noise() (which stays: learn() needs the learner's own sample) and act_batch(per_row_noise=True);
+    the default leaves today's launches exactly as they are (all S streams share the one online sample).
+    Returns the number of learn() calls made."""
+    S = env.streams
+    if S != mem.streams:
+        raise ValueError("train_device: the environment has %d streams, the memory %d" % (S, mem.streams))
+    clip = float(getattr(args, "reward_clip", 0) or 0)
+    lo, hi = getattr(env, "reward_range", (-float("inf"), float("inf")))
+    clip_needed = clip > 0 and (lo < -clip or hi > clip)
+    act_kw = dict(per_row_noise=True) if per_stream_noise else {}                 # (the default passes no per_row_noise at all)
+
+    def round_fn(states):
+        actions = agent.act_batch(states, device_out=True, **act_kw)              # main.py:153, all streams, stays on the device
+        next_states, rewards, nonterminals = env.step_device(actions)             # main.py:154 (ended streams: their reset stack)
+        if clip_needed:
+            rewards = rewards.clamp(-clip, clip)                                  # main.py:155-156
+        mem.append_streams(states, actions, rewards, nonterminals=nonterminals)   # main.py:157
+        return next_states
+
+    agent.train()
+    states = env.reset()
+    if S == 1:
+        states = states.unsqueeze(0)
+    return _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states, round_fn)
 
 
 def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None, per_stream_noise=False):
@@ -89,26 +99,12 @@ def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None, per_strea
     priority_weight_increase * S per round, one learn() per replay_frequency env steps (learn_owed), target update and on_eval
     at `T % k < S`.  per_stream_noise: as in train_device (one noise sample per emulator).  Returns the number of learn() calls made."""
     S = len(emus)
-    seed = int(getattr(args, "seed", 0))
     if S != mem.streams or S != front.streams:
         raise ValueError("train_host_vec: %d emulators, a front end of %d streams, a memory of %d" % (S, front.streams, mem.streams))
-    increase = (1 - args.priority_weight) / (T_max - args.learn_start)           # main.py:123
     clip = float(getattr(args, "reward_clip", 0) or 0)
-    eval_every = int(getattr(args, "evaluation_interval", 0) or 0)
-    agent.train()
-    scr = front.screens
-    for s in range(S):
-        emus[s].reset(scr[s, 0])
-    states = front.reset_all()
     flags, rewards, terminals = np.zeros(S, dtype=np.uint8), np.zeros(S, dtype=np.float32), np.zeros(S, dtype=bool)
-    learn_owed, learns = 0.0, 0
-    if per_stream_noise:
-        agent.reset_noise_rows(S, rng=(seed, 0))                                  # S < replay_frequency: the first rounds come before the first redraw
-    for T in range(1, T_max + 1, S):
-        if T % args.replay_frequency < S:
-            agent.reset_noise()                                                   # main.py:150-151
-            if per_stream_noise:
-                agent.reset_noise_rows(S, rng=(seed, T))
+
+    def round_fn(states):
         actions = agent.act_batch(states, per_row_noise=per_stream_noise)         # main.py:153, one forward for all streams
         scr = front.screens
         for s in range(S):
@@ -121,20 +117,13 @@ def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None, per_strea
             np.clip(rewards, -clip, clip, out=rewards)                            # main.py:155-156
         next_states = front.step(flags)
         mem.append_streams(states, actions, rewards, terminals)                   # main.py:157
-        if T >= args.learn_start:
-            mem.priority_weight = min(mem.priority_weight + increase * S, 1)      # main.py:161
-            learn_owed += S / args.replay_frequency
-            while learn_owed >= 1:
-                agent.learn(mem)                                                  # main.py:164
-                learn_owed -= 1
-                learns += 1
-            if on_eval is not None and eval_every and T % eval_every < S:         # main.py:166-170
-                on_eval(T)
-                agent.train()
-            if T % args.target_update < S:
-                agent.update_target_net()                                         # main.py:177-178
-        states = next_states
-    return learns
+        return next_states
+
+    agent.train()
+    scr = front.screens
+    for s in range(S):
+        emus[s].reset(scr[s, 0])
+    return _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, front.reset_all(), round_fn)
 
 
 def evaluate_device(agent, env, episodes):
@@ -168,6 +157,22 @@ def _evaluation_result(agent, returns, lengths, val_mem):
                 avg_Q=float(sum(float(q) for q in Qs) / len(Qs)) if Qs is not None else None, Qs=Qs)
 
 
+@contextmanager
+def _eval_mode(agent):
+    """agent.eval() for the block; the mode the agent came in is restored on the way out, also by an exception."""
+    was_training = agent.training
+    agent.eval()                                                                  # test.py:15 / main.py:168
+    try:
+        yield
+    finally:
+        if was_training:
+            agent.train()
+
+
+def _unfinished(who, missing, episodes, max_rounds):
+    return RuntimeError("%s: %d of %d episodes still unfinished after max_rounds = %d rounds" % (who, missing, episodes, max_rounds))
+
+
 def evaluate_vec(agent, env, episodes, epsilon=0.001, seed=0, val_mem=None, poll_every=8, max_rounds=None):
     """test.py:13-41 on `env`, a rainbow_amd.envs environment of S streams with a seed of its own: the agent in eval() mode,
     act_e_greedy with `epsilon` for every stream (Agent.act_batch(epsilon=..., rng=(seed, round)): the draw happens in the head
@@ -180,9 +185,7 @@ def evaluate_vec(agent, env, episodes, epsilon=0.001, seed=0, val_mem=None, poll
     The agent is left in the mode it came in."""
     S = env.streams
     poll_every = max(1, int(poll_every))
-    was_training = agent.training
-    agent.eval()                                                                  # test.py:15 / main.py:168
-    try:
+    with _eval_mode(agent):
         tally = EpisodeTally(S, episodes, env.device)
         states = env.reset()
         if S == 1:
@@ -199,14 +202,10 @@ def evaluate_vec(agent, env, episodes, epsilon=0.001, seed=0, val_mem=None, poll
                 if missing == 0:
                     break
                 if last:
-                    raise RuntimeError("evaluate_vec: %d of %d episodes still unfinished after max_rounds = %d rounds"
-                                       % (missing, episodes, max_rounds))
+                    raise _unfinished("evaluate_vec", missing, episodes, max_rounds)
         returns, lengths, _ = tally.result()
         tally.close()
         return _evaluation_result(agent, returns, lengths, val_mem)
-    finally:
-        if was_training:
-            agent.train()
 
 
 def evaluate_host_vec(agent, emus, front, episodes, epsilon=0.001, seed=0, val_mem=None, max_rounds=None):
@@ -225,9 +224,7 @@ def evaluate_host_vec(agent, emus, front, episodes, epsilon=0.001, seed=0, val_m
     recorded = [[] for _ in range(S)]
     ret, length = np.zeros(S, dtype=np.float32), np.zeros(S, dtype=np.int64)
     flags = np.zeros(S, dtype=np.uint8)
-    was_training = agent.training
-    agent.eval()
-    try:
+    with _eval_mode(agent):
         scr = front.screens
         for s in range(S):
             emus[s].reset(scr[s, 0])
@@ -235,8 +232,7 @@ def evaluate_host_vec(agent, emus, front, episodes, epsilon=0.001, seed=0, val_m
         missing, rounds = int(episodes), 0
         while missing > 0:
             if max_rounds is not None and rounds >= max_rounds:
-                raise RuntimeError("evaluate_host_vec: %d of %d episodes still unfinished after max_rounds = %d rounds"
-                                   % (missing, episodes, max_rounds))
+                raise _unfinished("evaluate_host_vec", missing, episodes, max_rounds)
             actions = agent.act_batch(states, epsilon=epsilon, rng=(seed, rounds))              # test.py:26
             scr = front.screens
             for s in range(S):
@@ -258,6 +254,3 @@ def evaluate_host_vec(agent, emus, front, episodes, epsilon=0.001, seed=0, val_m
             rounds += 1
         flat = [x for per_stream in recorded for x in per_stream]
         return _evaluation_result(agent, [x[0] for x in flat], [x[1] for x in flat], val_mem)
-    finally:
-        if was_training:
-            agent.train()
