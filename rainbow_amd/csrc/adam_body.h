@@ -1,5 +1,5 @@
 // adam_body.h — clip_grad_norm_ + Adam (agent.py:97-98) as a device body that a foreign launch can host.
-// k_clip_adam (adam_kernels.h) runs it as a launch of its own; k_sample (replay.hip) can carry it as extra workgroups: the
+// k_clip_adam (adam_kernels.h) runs it as a launch of its own; k_sample (replay_sample.h) can carry it as extra workgroups: the
 // optimiser pass of learn call k has no data dependency on the sampler of call k + 1 (it reads the gradient, its norm
 // partials and the moments; the sampler reads the sum-tree, whose write-back happened in call k's backward), so when two
 // learn calls follow each other the 6.4 M-parameter streaming pass runs beside the sampler's serial, latency-bound
@@ -116,7 +116,7 @@ __device__ __forceinline__ bool rb_adam_hosted_prologue(ClipAdamArgs& a, int eb,
 // while the data loads and the prologue are in flight, and read back for the update: as registers they pushed the hosting
 // sampler kernel over its 128-register budget (5 spilled VGPRs, a scratch segment: +10 us per step for EVERY kernel), and with
 // one pair per thread the pass streamed too thinly to gain anything (38.8 against 36.3 us for the hosting launch).
-#define RB_ADAM_PAIR_T 256            // hosted workgroups are 256 threads (replay.hip sample_impl)
+#define RB_ADAM_PAIR_T 256            // hosted workgroups are 256 threads (replay.hip sample_impl, adam_kernels.h k_adam_pending)
 __device__ __forceinline__ void rb_adam_hosted_pairs(ClipAdamArgs& a, int eb, int pb, float* s_red16) {
   constexpr int PU = 2;
   __shared__ float4 s_prod[PU * RB_ADAM_PAIR_T];
@@ -235,6 +235,6 @@ __device__ __forceinline__ void rb_adam_hosted_block(const ClipAdamArgs* ad, int
   }
 }
 
-// The pending pass as a launch of its own through the HOSTED body (replay.hip k_adam_pending; arguments in device memory): what
-// runs a pass with (mu, sigma) pairing outside a sampler launch.  Returns a hipError_t as int.
+// The pending pass as a launch of its own through the HOSTED body (adam_kernels.h k_adam_pending, in the learner's unit; arguments
+// in device memory): what runs a pass with (mu, sigma) pairing outside a sampler launch.  Returns RB_OK or RB_ERR_HIP.
 int rb_launch_adam_pending(const ClipAdamArgs* args_dev, int blocks, void* stream);

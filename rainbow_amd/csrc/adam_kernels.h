@@ -1,5 +1,5 @@
 // adam_kernels.h — the optimiser pass as launches of its own (adam_body.h has the element bodies and the hosted form).
-// Included by learner.hip only (non-template kernels).
+// Included by learner.hip only (non-template kernels, and rb_launch_adam_pending, which is defined here).
 #pragma once
 #include "learner_internal.h"
 
@@ -192,4 +192,18 @@ __global__ void k_store_adam_args(ClipAdamArgs a, ClipAdamArgs* dst) {
   if (blockIdx.x == 0 && threadIdx.x == 0) *dst = a;
 }
 
+// the pending optimiser pass (adam_body.h) as a launch of its own: flush_update (optimizer_host.h), and what the replay's
+// sample_impl falls back to when the sampler variant that can host the pass does not fit the replay's window length
+__global__ __launch_bounds__(256) void k_adam_pending(const ClipAdamArgs* ad) {
+  __shared__ float s_adam[18];
+  rb_adam_hosted_block<4>(ad, (int)blockIdx.x, (int)gridDim.x, s_adam);
+}
+
 }  // extern "C"
+
+// (declared in adam_body.h: replay.hip calls it across translation units)
+int rb_launch_adam_pending(const ClipAdamArgs* args_dev, int blocks, void* stream) {
+  RB_LAUNCH_T("clip_adam:k_adam_pending", k_adam_pending, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, args_dev);
+  RB_LAUNCH_CHECK();
+  return RB_OK;
+}

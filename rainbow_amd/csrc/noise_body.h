@@ -1,5 +1,5 @@
 // noise_body.h — factorised-Gaussian noise resampling (model.py:32-40) as a device body that any launch can host:
-// k_noise (noise_kernel.h) runs it alone; k_sample (replay.hip) can carry it as extra workgroups so that the per-step
+// k_noise (noise_kernel.h) runs it alone; k_sample (replay_sample.h) can carry it as extra workgroups so that the per-step
 // noise draw costs no kernel boundary of its own.
 #pragma once
 #include "rb_common.h"

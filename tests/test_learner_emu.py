@@ -401,12 +401,16 @@ def test_train_step_entry_point_equals_its_three_calls(emu):
     ad1.close(); ad2.close(); rp1.close(); rp2.close()
 
 
-@pytest.mark.parametrize("implicit_sigma,max_norm,gemm", [(False, None, False), (True, None, False), (False, 0.02, False), (True, 0.02, False),
-                                                          (True, None, True)],
+@pytest.mark.parametrize("implicit_sigma,max_norm,gemm,multi_step",
+                         [(False, None, False, None), (True, None, False, None), (False, 0.02, False, None), (True, 0.02, False, None),
+                          (True, None, True, None), (False, None, False, 21)],
                          ids=["stored-sigma-grad", "implicit-sigma-grad", "stored-sigma-grad-clip-bites", "implicit-sigma-grad-clip-bites",
-                              "implicit-sigma-grad-tiled-gemm"])
-def test_deferred_optimiser_pass_is_hosted_by_the_next_sampler_launch(emu, monkeypatch, implicit_sigma, max_norm, gemm):
-    """RB_LEARNER_IMPLICIT_SIGMA on top (second and third case): the backward does not store the hidden layer's sigma-weight
+                              "implicit-sigma-grad-tiled-gemm", "stored-sigma-grad-window-25"])
+def test_deferred_optimiser_pass_is_hosted_by_the_next_sampler_launch(emu, monkeypatch, implicit_sigma, max_norm, gemm, multi_step):
+    """Last case (multi_step 21, a window of 25 transitions): the sampler variant that hosts the pass holds windows of up to 24, so
+    rb_replay_sample_fused_noise launches the pending pass itself (rb_launch_adam_pending) in front of an un-hosted sampler — same
+    order in the stream, same twin, same bit-identity.
+    RB_LEARNER_IMPLICIT_SIGMA on top (second and third case): the backward does not store the hidden layer's sigma-weight
     gradient, the hosted pass forms it from g_mu and the noise snapshot while it updates the (mu, sigma) pairs, and whatever runs
     the pass as a launch of its own (act, flush) materialises it first — with a clip that bites (max_norm 0.02) the scaled
     gradients it stores back include sigma's.  Same twin, same bit-identity, the stored gradient included.
@@ -419,8 +423,11 @@ def test_deferred_optimiser_pass_is_hosted_by_the_next_sampler_launch(emu, monke
     import ctypes as C
     from rainbow_amd import _lib as L
     name = "dataeff"
+    if multi_step is not None:
+        name = "dataeff-n%d" % multi_step
+        monkeypatch.setitem(scenarios.LEARN_CONFIGS, name, dict(scenarios.LEARN_CONFIGS["dataeff"], multi_step=multi_step))
     c = scenarios.LEARN_CONFIGS[name]
-    # (the library enables the pairing from 1 M-element layers on; last case: the weight gradient comes from the tiled GEMM of
+    # (the library enables the pairing from 1 M-element layers on; fifth case: the weight gradient comes from the tiled GEMM of
     # fc_gemm.h — batch 256's path — whose epilogue leaves the sigma gradient out the same way)
     monkeypatch.setenv("RB_OPTS", "implicit_small=1,spec_draw=0" + (",fc_gemm=1" if gemm else ""))    # (the early draw has a twin test of its own)
     h1 = _ts_build(emu, name)

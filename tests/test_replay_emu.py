@@ -61,7 +61,7 @@ def test_sampler_deep_tree_matches_oracle(emu, capacity):
     hdr = ad.raw_header()
     assert hdr.index == ora.transitions.index and bool(hdr.full) == ora.transitions.full
     assert hdr.max == ora.transitions.max and hdr.total == ora.transitions.total()
-    for B in (32, 256):
+    for B in (32, 256, 257):         # 257: the smallest batch that reaches k_sample<1024, 4> (320 threads)
         uu = rs.random_sample((16, B))
         got = ad.sample(B, uu, 0.6)
         ora.priority_weight = 0.6
@@ -81,7 +81,7 @@ def test_sampler_deep_tree_matches_oracle(emu, capacity):
 @pytest.mark.parametrize("capacity", [64, 1000, 6000, 70000])
 def test_sorted_small_batch_update_matches_oracle(emu, capacity):
     """k_update's one-wave path for SORTED batches of at most 64 leaves (what ReplayMemory.sample hands to update_priorities:
-    stratified draws never decrease) — replay_internal.h rb_update_sorted_wave — against SegmentTree.update (memory.py:44-48):
+    stratified draws never decrease) — replay_update.h rb_update_sorted_wave — against SegmentTree.update (memory.py:44-48):
     runs of duplicate leaves (last write wins), sibling pairs, clusters that merge a few levels up, one leaf, 64 leaves, the
     first and the last leaf of the tree; then the same leaves shuffled (the hashed workgroup path) on a twin.  Tree, max and
     total bit-exact after every call."""
@@ -133,7 +133,7 @@ def test_sorted_small_batch_update_matches_oracle(emu, capacity):
 
 @pytest.mark.parametrize("capacity,n", [(6000, 3), (2000, 20)])
 def test_update_and_sample_in_one_launch_equals_the_two_calls(emu, capacity, n):
-    """k_update_sample (replay.hip) against rb_replay_update_priorities + rb_replay_sample on a twin (scenarios.py)."""
+    """k_update_sample (replay_sample.h) against rb_replay_update_priorities + rb_replay_sample on a twin (scenarios.py)."""
     scenarios.update_sample_twin_check(lambda c, h, nn: CAbiReplayAdapter(emu, NumpyMem(), c, h, nn, 0.99, 0.5), capacity=capacity, n=n)
 
 
@@ -149,6 +149,27 @@ def test_create_rejects_what_the_reference_cannot_run(emu):
         assert emu.rb_last_error()
     with pytest.raises(L.RainbowError):
         L.check(emu, emu.rb_replay_create(C.byref(C.c_void_p()), 501, 4, 3, 0.99, 0.5, 1))
+
+
+def test_wide_sampler_refuses_windows_longer_than_24(emu):
+    """The 1024-thread sampler variant (batch > 256) holds windows of up to 24 transitions: on a replay with history 4 and
+    multi_step 21 a batch of 257 is refused with a message that names the limit, and a batch of 32 (the 256-thread variant) is
+    drawn as usual."""
+    from rainbow_amd import _lib as L
+    rs = np.random.RandomState(3)
+    ad = CAbiReplayAdapter(emu, NumpyMem(), 2000, 4, 21, 0.99, 0.5)
+    n = 2100                                                    # full, write head at 100
+    ts = (np.arange(n) % 300).astype(np.int32)                  # an episode start every 300 transitions
+    frames = rs.randint(0, 256, size=(8, 84, 84)).astype(np.uint8)[np.arange(n) % 8]
+    actions, rewards = rs.randint(0, 4, n).astype(np.int32), rs.choice([-1.0, 0.0, 1.0], size=n).astype(np.float32)
+    for sl in (slice(0, 2000), slice(2000, n)):
+        ad.append_batch(frames[sl], ts[sl], actions[sl], rewards[sl], (ts[sl] != 299).astype(np.uint8))
+    with pytest.raises(L.RainbowError) as e:
+        ad.sample(257, np.random.RandomState(4).random_sample((16, 257)), 0.6)
+    assert "history + multi_step <= 24" in str(e.value)
+    got = ad.sample(32, np.random.RandomState(5).random_sample((16, 32)), 0.6)
+    assert ad.raw_header().last_status == 0 and got["tree_idxs"].shape == (32,)
+    ad.close()
 
 
 def test_earlier_valid_batch_survives_a_failed_draw(emu):

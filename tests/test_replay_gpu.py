@@ -391,7 +391,7 @@ def test_sampler_indices_match_oracle_at_100k_nstep20(hip):
     cap = 100_000
     mem = ReplayMemory(_args(multi_step=20), cap, seed=8)
     _fill_full(mem, cap, 20_000, 3)
-    _check_sampler_against_oracle(hip, mem, (32, 256), seed=78)
+    _check_sampler_against_oracle(hip, mem, (32, 256, 257), seed=78)      # 257: k_sample<1024, 4>, whose window limit is this 24
 
 
 def test_device_rng_sampler_frequencies(hip):
