@@ -229,6 +229,83 @@ int rb_catch_stats(rb_catch_t* c, rb_catch_stats_t* out_host, rb_stream_t stream
 /* Zero those totals (stream-ordered, asynchronous). */
 int rb_catch_reset_stats(rb_catch_t* c, rb_stream_t stream);
 
+/* ============================================================= device Breakout ==
+ * A second built-in environment on the device, with what Catch lacks: lives (a lost life is a terminal for training while the
+ * game goes on, env.py:70-75), episodes of varying length, rewards inside an episode and rewards above 1 (so that reward
+ * clipping, main.py:155-156, matters).  S independent games, one workgroup per stream, the same buffers as device Catch.
+ * Rules (all integer):
+ *  - logical grid 12 x 12, one cell = 7 x 7 pixels.  Ball: 1 cell at intensity 1.0; bricks: rows 1, 2, 3, 36 of them, at 0.75;
+ *    paddle: 2 cells wide on row 11 at 0.5, its left cell p in [0, 10]; background 0 (255, 191, 127 and 0 after the replay's
+ *    x * 255 truncation).  Row r keeps a 12-bit mask, bit c = column c.  The ball is at (bx, by), by in [0, 10], and moves
+ *    by (dx, dy), both in {-1, +1}.  It is never on a brick cell.  3 lives per game; t counts the steps of the game in play;
+ *    max_steps ends a game as ALE's max_num_frames_per_episode does;
+ *  - serve k (0, 1, 2, ...; per stream, 0xFFFFFFFF before the first reset) of stream s: (x0, x1, x2, .) = Philox4x32-10(key =
+ *    seed, counter = (lo = k, hi = s)), the generator of device Catch; bx = x0 % 12, by = 4, dx = (x1 & 1) ? +1 : -1, dy = +1;
+ *  - a new game is a serve that also sets p = x2 % 11, refills all bricks, sets lives = 3 and t = 0;
+ *  - one step with action a (0 stay, 1 left, 2 right; 3 actions; any other value counts as stay), in this order:
+ *      1. a == 1: p = max(p - 1, 0);  a == 2: p = min(p + 1, 10)
+ *      2. t += 1; reward = 0; lost = over = false
+ *      3. nx = bx + dx; if nx < 0 or nx > 11: dx = -dx, nx = bx + dx
+ *         ny = by + dy; if ny < 0:            dy = +1,  ny = by + dy
+ *      4. if 1 <= ny <= 3 and brick (ny, nx) stands: remove it, reward = 5 - ny, dy = -dy (the ball does not move this step)
+ *         else if ny == 11:
+ *              if p <= nx <= p + 1: bx = nx, dy = -1, dx = (nx == p) ? -1 : +1 (by stays 10); if no brick is left: refill all 36
+ *              else:                lives -= 1, lost = true, over = (lives == 0)
+ *         else: bx = nx, by = ny
+ *      5. if t == max_steps: over = true
+ *      6. if over: new game (k += 1); else if lost: serve (k += 1; bricks, paddle, lives and t stay)
+ *    Bricks pay 2 / 3 / 4 in rows 3 / 2 / 1;
+ *  - outputs of a step: reward f32 (0, 2, 3 or 4); nonterminal 0 where over, and with life_terminals != 0 also where lost, else
+ *    1; stacks_out[s] = where over, the reset stack of the new game (history - 1 zero frames, then its first observation,
+ *    env.py:40-52), otherwise stacks_in[s] shifted by one frame with the render of the NEW state last — after a lost life that
+ *    is the serve state: the stack moves one frame per round and is not blanked (the convention of the host emulators' loop);
+ *  - totals per stream: steps, bricks hit, lives lost, games finished, and return_sum = the sum of the returns (all rewards of
+ *    a game, unclipped) of the games FINISHED; game_return is the return so far of the game in play.                       */
+typedef struct rb_breakout rb_breakout_t;
+/* The whole state of one stream, 64 bytes, the device's own layout (exact checkpoints, and states random play never reaches). */
+typedef struct {
+  int32_t bx, by;       /* ball cell: column in [0, 11], row in [0, 10] */
+  int32_t dx, dy;       /* -1 or +1 each */
+  int32_t paddle;       /* left cell, in [0, 10] */
+  int32_t t;            /* steps of the game in play, in [0, max_steps) */
+  uint32_t k;           /* number of the last serve (0xFFFFFFFF: none yet) */
+  uint16_t rows[3];     /* bricks of rows 1, 2, 3: bit c = column c */
+  uint16_t lives;       /* in [1, 3] */
+  int32_t game_return;  /* rewards of the game in play */
+  int32_t games, return_sum, bricks, lives_lost, steps;   /* totals since create / rb_breakout_reset_stats, all >= 0 */
+  int32_t reserved;     /* 0 */
+} rb_breakout_state_t;
+typedef struct {
+  int64_t games;        /* games finished since create / rb_breakout_reset_stats, all streams */
+  double return_sum;    /* sum of their returns (unclipped) */
+  int64_t bricks;       /* bricks hit */
+  int64_t lives_lost;
+  int64_t steps;
+} rb_breakout_stats_t;
+#define RB_BREAKOUT_ACTIONS 3
+/* 1 <= streams <= 64, 1 <= history <= 16, 1 <= max_steps <= 65535. */
+int rb_breakout_create(rb_breakout_t** out, int32_t streams, int32_t history, int32_t max_steps, uint64_t seed);
+int rb_breakout_destroy(rb_breakout_t* c);
+/* Every stream starts its next game (the first call serves k = 0); the game in play is abandoned and counts nothing.
+ * stacks_dev gets the S reset stacks.  Asynchronous.                                                                       */
+int rb_breakout_reset(rb_breakout_t* c, float* stacks_dev, rb_stream_t stream);
+/* One step of every stream (one launch, asynchronous), operands as rb_catch_step's; life_terminals != 0 (training) reports a
+ * lost life as nonterminal 0.  Same refusals as rb_catch_step: NULL or misaligned operands, stacks_out_dev overlapping
+ * stacks_in_dev, no rb_breakout_reset or rb_breakout_set_state before it (RB_ERR_STATE).                                    */
+int rb_breakout_step(rb_breakout_t* c, const int32_t* actions_dev, const float* stacks_in_dev, float* stacks_out_dev,
+                     float* rewards_dev, uint8_t* nonterminals_dev, int32_t life_terminals, rb_stream_t stream);
+/* The totals, summed over the streams.  SYNCHRONISES `stream`. */
+int rb_breakout_stats(rb_breakout_t* c, rb_breakout_stats_t* out_host, rb_stream_t stream);
+/* Zero the totals (game_return stays: the game in play goes on).  Stream-ordered, asynchronous. */
+int rb_breakout_reset_stats(rb_breakout_t* c, rb_stream_t stream);
+/* The states of all S streams to host memory.  SYNCHRONISES `stream`. */
+int rb_breakout_get_state(rb_breakout_t* c, rb_breakout_state_t* out_host, rb_stream_t stream);
+/* Replace the states of all S streams.  Every field of every stream is validated first (the ranges above, t < max_steps, rows
+ * below 4096, the ball not on a brick cell, totals and game_return >= 0, reserved 0): RB_ERR_INVALID names the stream and the
+ * field, and nothing is changed.  Marks the handle as reset; the frame stacks are the caller's to restore.  SYNCHRONISES
+ * `stream`.                                                                                                             */
+int rb_breakout_set_state(rb_breakout_t* c, const rb_breakout_state_t* in_host, rb_stream_t stream);
+
 /* ================================================================ episode tally ==
  * An environment-independent recorder of per-episode returns on the device (test.py:19-41 keeps the list T_rewards): fed with
  * the rewards / nonterminals vectors every round already produces, so that an evaluation round on a device environment

@@ -57,6 +57,19 @@ class CatchStats(C.Structure):
     _fields_ = [("episodes", c_int64), ("catches", c_int64), ("return_sum", c_double)]
 
 
+class BreakoutState(C.Structure):
+    """rb_breakout_state_t (include/rainbow_hip.h): one stream, 64 bytes."""
+    _fields_ = [("bx", c_int32), ("by", c_int32), ("dx", c_int32), ("dy", c_int32), ("paddle", c_int32), ("t", c_int32),
+                ("k", C.c_uint32), ("rows", C.c_uint16 * 3), ("lives", C.c_uint16), ("game_return", c_int32),
+                ("games", c_int32), ("return_sum", c_int32), ("bricks", c_int32), ("lives_lost", c_int32), ("steps", c_int32),
+                ("reserved", c_int32)]
+
+
+class BreakoutStats(C.Structure):
+    """rb_breakout_stats_t (include/rainbow_hip.h)."""
+    _fields_ = [("games", c_int64), ("return_sum", c_double), ("bricks", c_int64), ("lives_lost", c_int64), ("steps", c_int64)]
+
+
 # name -> (restype, argtypes); every symbol include/rainbow_hip.h declares
 SIGNATURES = {
     "rb_last_error": (c_char_p, []),
@@ -88,6 +101,14 @@ SIGNATURES = {
     "rb_catch_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rb_catch_stats": (c_int, [c_void_p, C.POINTER(CatchStats), c_void_p]),
     "rb_catch_reset_stats": (c_int, [c_void_p, c_void_p]),
+    "rb_breakout_create": (c_int, [C.POINTER(c_void_p), c_int32, c_int32, c_int32, c_uint64]),
+    "rb_breakout_destroy": (c_int, [c_void_p]),
+    "rb_breakout_reset": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "rb_breakout_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "rb_breakout_stats": (c_int, [c_void_p, C.POINTER(BreakoutStats), c_void_p]),
+    "rb_breakout_reset_stats": (c_int, [c_void_p, c_void_p]),
+    "rb_breakout_get_state": (c_int, [c_void_p, C.POINTER(BreakoutState), c_void_p]),
+    "rb_breakout_set_state": (c_int, [c_void_p, C.POINTER(BreakoutState), c_void_p]),
     "rb_tally_create": (c_int, [C.POINTER(c_void_p), c_int32, c_int32]),
     "rb_tally_destroy": (c_int, [c_void_p]),
     "rb_tally_reset": (c_int, [c_void_p, c_void_p]),

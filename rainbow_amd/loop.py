@@ -3,7 +3,9 @@
 A round is launches on one stream and nothing else: Agent.act_batch(device_out=True) -> env.step_device ->
 ReplayMemory.append_streams with device operands -> Agent.learn.  Actions, rewards, nonterminals and the per-stream episode
 timesteps never reach the host, and no call in a round synchronises (Agent.learn reports a sampler that found no batch one
-call late, from pinned memory).  `env` is a rainbow_amd.envs environment (CatchVec) with as many streams as `mem`.
+call late, from pinned memory).  `env` is a rainbow_amd.envs environment (CatchVec, BreakoutVec) with as many streams as `mem`.
+An environment with lives (BreakoutVec in training mode) reports a lost life as nonterminals == 0 while its next stack is the
+old one moved on, not a reset stack (env.py:70-75); the loop needs to know nothing about it.
 
 `train_host_vec` is the same loop for S raw HOST emulators (ALE) behind a rainbow_amd.frames.FrameStackVec: the emulators write
 their u8 screens into the front end's pinned staging, one upload and one launch per round build all S frame stacks.
@@ -180,6 +182,9 @@ def evaluate_vec(agent, env, episodes, epsilon=0.001, seed=0, val_mem=None, poll
     EpisodeTally.step, launches only; the number of episodes still missing is polled (one synchronisation) every `poll_every`
     rounds.  Stream s contributes its first episodes // S + (s < episodes % S) episodes, so short episodes are not
     over-represented; the list is stream-major.  More than `max_rounds` rounds (None = no bound) raise RuntimeError.
+    The caller hands over an environment in EVALUATION mode (test.py:17 builds its env and calls env.eval()): an episode is a
+    whole game, so an environment with lives must not report a lost life as a terminal — BreakoutVec(training=False) or
+    env.eval() before the call; a training-mode environment would have every life recorded as an episode.
     Returns dict(avg_reward, rewards, lengths, avg_Q, Qs): `rewards` has exactly `episodes` entries; Qs is
     agent.evaluate_q_memory(val_mem) (test.py:38-39) and avg_Q its mean when a validation memory is given, else None.
     The agent is left in the mode it came in."""

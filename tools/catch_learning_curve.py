@@ -4,7 +4,11 @@ defaults) through rainbow_amd.loop.train_device, with the options tests/golden/m
 Every --t-eval env steps the agent is evaluated in eval() mode over 256 episodes on a fresh environment with a fixed seed.
 One line per checkpoint; `--no-learn` runs the same loop with learn() skipped (what an agent that does not learn scores).
 `--protocol vec` evaluates with rainbow_amd.loop.evaluate_vec instead (test.py's protocol: epsilon 0.001, 256 episodes spread
-evenly over the streams); the default, `device`, is evaluate_device as before."""
+evenly over the streams); the default, `device`, is evaluate_device as before.
+`--env breakout` runs the same on the device Breakout environment (training: a lost life is a terminal; evaluation: whole
+games, unclipped returns), same output format.  `--multi-step` / `--learn-start` override the recipe's 20 / 1600: with them the
+stratified draw needs more than batch_size * (multi_step + 1) * S stored transitions, and its last stratum must not fall inside
+the multi_step newest slots, which all carry the running max priority (Agent.learn raises; the line then ends in STOPPED)."""
 import argparse
 import os
 import sys
@@ -20,24 +24,25 @@ sys.path.insert(0, ROOT)
 EVAL_SEED = 777_001
 
 
-def options(t_max, dev):
+def options(t_max, dev, multi_step=20, learn_start=1600):
     return types.SimpleNamespace(
-        device=dev, architecture="data-efficient", hidden_size=256, multi_step=20, learning_rate=1e-4, replay_frequency=1,
+        device=dev, architecture="data-efficient", hidden_size=256, multi_step=multi_step, learning_rate=1e-4, replay_frequency=1,
         target_update=2000, batch_size=32, atoms=51, V_min=-10.0, V_max=10.0, history_length=4, noisy_std=0.1, discount=0.99,
-        priority_exponent=0.5, priority_weight=0.4, adam_eps=1.5e-4, norm_clip=10.0, reward_clip=1, learn_start=1600,
+        priority_exponent=0.5, priority_weight=0.4, adam_eps=1.5e-4, norm_clip=10.0, reward_clip=1, learn_start=learn_start,
         model=None, T_max=t_max)
 
 
-def run(S, seed, t_max, t_eval, learn, dev, protocol="device"):
+def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", multi_step=20, learn_start=1600):
     from rainbow_amd.agent import Agent
-    from rainbow_amd.envs import CatchVec
+    from rainbow_amd.envs import BreakoutVec, CatchVec
     from rainbow_amd.loop import evaluate_device, evaluate_vec, train_device
     from rainbow_amd.memory import ReplayMemory
-    args = options(t_max, dev)
+    make = {"catch": CatchVec, "breakout": BreakoutVec}[game]
+    args = options(t_max, dev, multi_step, learn_start)
     args.evaluation_interval = t_eval
     np.random.seed(seed)
     torch.manual_seed(np.random.randint(1, 10000))
-    env = CatchVec(S, dev, seed=seed)
+    env = make(S, dev, seed=seed)
     agent = Agent(args, env)
     cap = -(-t_max // (2 * S)) * 2 * S
     mem = ReplayMemory(args, cap, seed=seed, streams=S)
@@ -46,7 +51,8 @@ def run(S, seed, t_max, t_eval, learn, dev, protocol="device"):
     curve = []
 
     def on_eval(T):
-        ev = CatchVec(16, dev, seed=EVAL_SEED)
+        ev = make(16, dev, seed=EVAL_SEED)
+        ev.eval()
         if protocol == "vec":
             curve.append((T, evaluate_vec(agent, ev, 256, seed=T)["avg_reward"]))
         else:
@@ -74,13 +80,16 @@ def main():
     ap.add_argument("--seeds", type=int, default=5)
     ap.add_argument("--no-learn", action="store_true")
     ap.add_argument("--protocol", choices=["device", "vec"], default="device")
+    ap.add_argument("--env", choices=["catch", "breakout"], default="catch")
+    ap.add_argument("--multi-step", type=int, default=20)
+    ap.add_argument("--learn-start", type=int, default=1600)
     a = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
     dev = torch.device("cuda", 0)
     for S in a.streams:
         for k in range(a.seeds if S == 1 else min(3, a.seeds)):
-            run(S, 101 + 7 * k, a.t_max, a.t_eval, not a.no_learn, dev, a.protocol)
+            run(S, 101 + 7 * k, a.t_max, a.t_eval, not a.no_learn, dev, a.protocol, a.env, a.multi_step, a.learn_start)
 
 
 if __name__ == "__main__":
