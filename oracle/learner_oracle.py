@@ -125,15 +125,21 @@ def noisy_linear(x, params, layer, noise):
     return x @ w.t() + b
 
 
-def forward(cfg, params, noise, x, log=False, probe=None, hidden_mask=None):
+def forward(cfg, params, noise, x, log=False, probe=None, hidden_mask=None, conv_masks=None):
     """DQN.forward (model.py:69-80).  x float32 [B,h,84,84] in [0,1]; params: torch tensors.
     probe (optional dict): receives 'hidden_relu_margin' = the smallest |pre-activation| of the two hidden layers (see learn)
     and 'hidden_pre' = the two pre-activation matrices (numpy).
     hidden_mask (optional, test hook): boolean [B, 2H] — the hidden layers' ReLU decisions (value stream | advantage stream) are
-    TAKEN from it instead of from the sign of this forward's own pre-activations (see learn)."""
+    TAKEN from it instead of from the sign of this forward's own pre-activations (see learn).
+    conv_masks (optional, test hook): one boolean [B, cout, oh, ow] per conv layer — the same for the conv layers' ReLUs; probe then
+    also receives 'conv_pre' (the conv pre-activations, numpy, per layer) and 'conv_in' (each layer's input)."""
     convs, feat = cfg.convs
     for i, (_c, _k, stride) in enumerate(convs):
-        x = F.relu(F.conv2d(x, params["convs.%d.weight" % (2 * i)], params["convs.%d.bias" % (2 * i)], stride=stride))
+        pre = F.conv2d(x, params["convs.%d.weight" % (2 * i)], params["convs.%d.bias" % (2 * i)], stride=stride)
+        if probe is not None and conv_masks is not None:
+            probe.setdefault("conv_pre", []).append(pre.detach().numpy())
+            probe.setdefault("conv_in", []).append(x.detach().numpy())
+        x = pre * _t(np.asarray(conv_masks[i])).to(torch.float32) if conv_masks is not None else F.relu(pre)
     x = x.reshape(-1, feat)                                                    # model.py:71
     pre_v, pre_a = noisy_linear(x, params, "fc_h_v", noise), noisy_linear(x, params, "fc_h_a", noise)
     if probe is not None:
@@ -178,7 +184,7 @@ def project(cfg, pns_a, returns, nonterminals):
     return m, l, u, b
 
 
-def learn(cfg, online, target, noise_online, noise_target, batch, hidden_mask=None):
+def learn(cfg, online, target, noise_online, noise_target, batch, hidden_mask=None, conv_masks=None):
     """Agent.learn up to and including backward (agent.py:63-96).
     online/target: {name: np.float32 array}; batch: dict(states u8[B,h,84,84], next_states u8,
     actions i64[B], returns f32[B], nonterminals f32[B] or [B,1], weights f32[B]).
@@ -193,7 +199,11 @@ def learn(cfg, online, target, noise_online, noise_target, batch, hidden_mask=No
     `hidden_mask_flips` = how many of its own decisions differ and `hidden_mask_flip_abs` = the largest |pre-activation| among
     those: a parity test at batch 256 (262 144 pre-activations per step, the smallest ~3e-8, a split-K GEMM's summation noise
     ~5e-8) uses it to show that every difference it tolerates IS this discontinuity — decisions that differ only where the
-    pre-activation is inside the rounding noise — and nothing else."""
+    pre-activation is inside the rounding noise — and nothing else.
+    conv_masks (optional, test hook; one boolean [B, cout, oh, ow] per conv layer): the same for the conv layers' ReLUs (B * 21 120
+    pre-activations per step in the canonical net: some sit inside the rounding noise of a K-term f32 dot product at any batch of
+    a hundred samples).  The result then carries `conv_pre` and `conv_in` (per layer: this forward's pre-activations and inputs) for
+    the caller to judge the decisions that differ."""
     B = batch["states"].shape[0]
     p_on = {k: _t(v).clone().requires_grad_(True) for k, v in online.items()}
     p_tg = {k: _t(v) for k, v in target.items()}
@@ -205,7 +215,7 @@ def learn(cfg, online, target, noise_online, noise_target, batch, hidden_mask=No
     weights = _t(batch["weights"]).to(torch.float32)
 
     probe = {}
-    log_ps = forward(cfg, p_on, noise_online, states, log=True, probe=probe, hidden_mask=hidden_mask)   # agent.py:66
+    log_ps = forward(cfg, p_on, noise_online, states, log=True, probe=probe, hidden_mask=hidden_mask, conv_masks=conv_masks)   # agent.py:66
     log_ps_a = log_ps[torch.arange(B), actions]                                # agent.py:67
     with torch.no_grad():
         pns = forward(cfg, p_on, noise_online, next_states)                    # agent.py:71
@@ -219,7 +229,8 @@ def learn(cfg, online, target, noise_online, noise_target, batch, hidden_mask=No
     return dict(loss=loss.detach().numpy().copy(), m=m.numpy().copy(), a_star=a_star.numpy().copy(),
                 pns_a=pns_a.numpy().copy(), log_ps_a=log_ps_a.detach().numpy().copy(), grads=grads,
                 l=l.numpy().copy(), u=u.numpy().copy(), hidden_relu_margin=probe["hidden_relu_margin"],
-                **(_mask_flips(probe["hidden_pre"], hidden_mask) if hidden_mask is not None else {}))
+                **(_mask_flips(probe["hidden_pre"], hidden_mask) if hidden_mask is not None else {}),
+                **(dict(conv_pre=probe["conv_pre"], conv_in=probe["conv_in"]) if conv_masks is not None else {}))
 
 
 def _mask_flips(pre, mask):

@@ -538,7 +538,7 @@ int rb_debug_occupancy(void) {
 #endif
 int rb_learner_debug_read(rb_learner_t* l, int32_t what, void* out_dev, rb_stream_t stream) {
   RB_REQUIRE(l && out_dev, "rb_learner_debug_read: NULL argument");
-  if (what != 5) RB_FLUSH_UPDATE(l, stream);     // (5 is an activation of the last learn call: a pending optimiser pass stays pending)
+  if (what < 5) RB_FLUSH_UPDATE(l, stream);      // (5 .. 8 are activations of the last learn call: a pending optimiser pass stays pending)
   const Layout& L = l->L;
   const void* src = nullptr;
   size_t bytes = 0;
@@ -549,6 +549,12 @@ int rb_learner_debug_read(rb_learner_t* l, int32_t what, void* out_dev, rb_strea
     case 3: src = l->pns_a; bytes = (size_t)L.B * L.Z * 4; break;
     case 4: src = l->logits; bytes = (size_t)3 * L.B * L.NZ * 4; break;
     case 5: src = l->h; bytes = (size_t)L.B * 2 * L.H * 4; break;     // hidden activations of the differentiated forward (rows [0, B))
+    case 6: case 7: case 8: {                                         // conv layer (what - 6)'s activations of the same forward: [B][cout][P]
+      const int layer = what - 6;
+      RB_REQUIRE(layer < L.nconv, "rb_learner_debug_read: the network has no such conv layer");
+      src = l->act[layer]; bytes = (size_t)L.B * L.conv[layer].cout * L.conv[layer].oh * L.conv[layer].oh * 4;
+      break;
+    }
     default: rb_set_error("rb_learner_debug_read: unknown selector %d", what); return RB_ERR_INVALID;
   }
   RB_HIP_TRY(hipMemcpyAsync(out_dev, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));

@@ -167,6 +167,41 @@ def test_batch_64_conv_input_gradient_image_loop_and_the_forward_only_gemm(emu):
     assert hi["fc_h_bwd"]["gemm_bwd"] == 0
 
 
+@pytest.mark.parametrize("batch", [86, 100, 129, 257])
+def test_batches_without_a_multiple_of_8_groups_get_one_image_group(emu, batch):
+    """No images-per-workgroup count at or above the one-round estimate divides these batches into a multiple of 8 groups, and
+    round_ipb_to_groups_of_8 counts on to the batch itself: ONE image group, 2 to 25 workgroups that walk the whole batch with their
+    weight slab resident.  Keeping the one-round estimate instead (86 / 43 groups at batch 86, ...) was measured and is no faster —
+    profiles/dx_group_rounding.txt: batch 100 +1 .. +3.5 us per step, batch 257 equal — so the plan stays; at default options the
+    image loops of the data-gradient kernels therefore never see a SHORT last group, and tests/test_learner_batches_gpu.py
+    reaches one through RB_OPTS dx_ipb, pinned here as well."""
+    ceil = lambda a, b: -(-a // b)
+    p = plan(emu, batch=batch)
+    for tag, phases, cit in (("conv3_dx", 1, 2), ("conv2_dx", 4, 1)):
+        r = p[tag]
+        assert base(r["kernel"]) == "k_conv_dx_t16_multi" and r["ipb"] == batch and r["img_fast"] == 0 and r["grid"] == (phases, cit, 1), (tag, r)
+    d = plan(emu, batch=batch, **DATA_EFF)["conv2_dx"]
+    assert d["kernel"] == "k_conv_dx_lds<GeomD2,MULTI=true>" and d["ipb"] == batch and d["img_fast"] == 0 and d["grid"] == (25, 1, 1), d
+    for ipb in (2, 5):      # the hook: the count as given, (phase, tile, group) order, a short last group
+        q = plan(emu, batch=batch, opts="dx_ipb=%d" % ipb)
+        for tag in ("conv3_dx", "conv2_dx"):
+            assert q[tag]["ipb"] == ipb and q[tag]["grid"][2] == ceil(batch, ipb) and q[tag]["img_fast"] == (1 if batch % ipb == 0 and (batch // ipb) % 8 == 0 else 0)
+        e = plan(emu, batch=batch, opts="dx_ipb=%d" % ipb, **DATA_EFF)["conv2_dx"]
+        assert e["kernel"] == "k_conv_dx_lds<GeomD2,MULTI=true>" and e["ipb"] == ipb and e["grid"][2] == ceil(batch, ipb)
+    if batch == 129:      # dx_ipb=2: 64 groups of two images and one of a single image
+        assert plan(emu, batch=129, opts="dx_ipb=2")["conv3_dx"]["grid"] == (1, 2, 65)
+
+
+@pytest.mark.parametrize("batch,c3,c2,d2", [(64, (1, 64), (1, 64), (8, 8)), (128, (1, 128), (2, 64), (16, 8)), (200, (5, 40), (5, 40), (25, 8)),
+                                            (256, (2, 128), (4, 64), (32, 8)), (320, (4, 80), (5, 64), (40, 8)),
+                                            (1024, (8, 128), (16, 64), (128, 8))])
+def test_batches_with_a_multiple_of_8_groups_are_rounded_to_them(emu, batch, c3, c2, d2):
+    """(images per workgroup, groups) of the data-gradient launches where the rounding exists: image-group-fastest order."""
+    p, d = plan(emu, batch=batch), plan(emu, batch=batch, **DATA_EFF)
+    for r, (ipb, ng) in ((p["conv3_dx"], c3), (p["conv2_dx"], c2), (d["conv2_dx"], d2)):
+        assert r["ipb"] == ipb and r["img_fast"] == 1 and r["grid"][0] == ng and ipb * ng == batch, r
+
+
 def test_backward_gemm_starts_at_batch_128(emu):
     lo, hi = plan(emu, batch=127), plan(emu, batch=128)
     assert lo["fc_h_fwd"]["kernel"] == "k_fc_gemm_fwd" and lo["fc_h_bwd"]["kernel"] == "k_nl_bwd<false>" and lo["fc_h_bwd"]["gemm_bwd"] == 0

@@ -153,6 +153,10 @@ AGENT_SHAPES = {
     "baseline-cfg2-h512-b32-a6": ("canonical", 512, 32, 6, 3, 4096, 6000, 31),
     "baseline-cfg3-h512-b256-a4": ("canonical", 512, 256, 4, 3, 8192, 12000, 31),
     "baseline-cfg4-dataeff-h256-n20": ("data-efficient", 256, 32, 6, 20, 16384, 20000, 31),
+    # above batch 256: the 1024-thread sampler variant (k_sample<1024, ...> drawing 320 samples), the pending optimiser pass as a launch
+    # of its own in front of it (optimizer_host.h attach_pending_pass: batch > 256 is not hosted) and the priority write-back
+    # outside the hidden layer's launch (learner_plan.h plan_fc_bwd: up_enabled needs B <= 256)
+    "dataeff-h256-b320-a6": ("data-efficient", 256, 320, 6, 3, 8192, 12000, 31),
 }
 AGENT_STEPS = 6
 RELU_MARGIN = 3e-8      # ~10x the f32 rounding noise of a hidden pre-activation (oracle.learner_oracle.learn: hidden_relu_margin)
@@ -250,7 +254,10 @@ def _assert_params_track(got, want, atol, flip_atol, flip_frac, msg):
 
 @pytest.mark.parametrize("shape", sorted(AGENT_SHAPES))
 def test_agent_default_flag_set_with_hosted_optimiser_pass_vs_oracle(hip, shape):
-    """The EXACT configuration bench.py times at BASELINE configs 2, 3 and 4, against the oracle (agent.py:61-100,
+    """The EXACT configuration bench.py times at BASELINE configs 2, 3 and 4 — and one shape above batch 256, where the pending
+    pass is NOT hosted: the sampler launch takes no tenants beyond 256 samples, so call k + 1 runs call k's pass as a launch of its
+    own in front of its sampler, and the priority write-back is a launch of its own as well; everything below about reading the
+    parameters raw after call k + 1 holds there unchanged — against the oracle (agent.py:61-100,
     memory.py:124-159): `Agent` with its defaults — RB_LEARNER_DEFER_UPDATE (+ RB_LEARNER_IMPLICIT_SIGMA where the hidden
     layer is large enough) — so that the clip + Adam pass of learn call k runs as tenant workgroups of call k + 1's SAMPLER
     launch (k_sample<1024, 4> hosting the paired (mu, sigma) optimiser body; 256 samples at config 3, where the backward is
@@ -320,7 +327,7 @@ def test_agent_default_flag_set_with_hosted_optimiser_pass_vs_oracle(hip, shape)
         if was_pending:
             assert agent._update_pending, "step %d" % step
             hosted += 1
-            got = raw_params()      # = the parameters after step - 1's update, which this call's sampler launch hosted
+            got = raw_params()      # = the parameters after step - 1's update, which this call's sampler launch hosted (above batch 256: which this call ran in front of its sampler)
             prev = want[step - 1]
             for k in prev["params"]:
                 _assert_params_track(got[k], prev["params"][k], p_atol, flip_atol, flip_frac, "hosted pass of step %d: %s" % (step - 1, k))
@@ -334,7 +341,7 @@ def test_agent_default_flag_set_with_hosted_optimiser_pass_vs_oracle(hip, shape)
     assert hosted >= 4, hosted
     if big:
         want_tree = stepper.tree()
-        print("cfg-3 ReLU decisions that differed from the oracle's own, per step:", [(w["flips"], "%.1e" % w["flip_abs"]) for w in want])
+        print(shape, "ReLU decisions that differed from the oracle's own, per step:", [(w["flips"], "%.1e" % w["flip_abs"]) for w in want])
     got = {k: v.cpu().numpy() for k, v in agent.state_dict().items() if "epsilon" not in k}      # (flushes the last pass)
     for k in got:
         _assert_params_track(got[k], want[-1]["params"][k], p_atol, flip_atol, flip_frac, "final %s" % k)
