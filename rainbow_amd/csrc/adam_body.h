@@ -65,7 +65,10 @@ __device__ __forceinline__ void rb_adam_quad(float4& P, float4& G, float4& M, fl
   rb_adam_elem(P.w, G.w, M.w, V.w, coef, a);
 }
 
-// The plain pass (no skipped range) as hosted workgroups: block `eb` of `nblk`, any block size that is a multiple of 64.
+// The plain pass (no skipped range) as hosted workgroups: block `eb` of `nblk`.  The element loops work for any block size that
+// is a multiple of 64, but the prologue hands norm partial i to thread i % blockDim.x, so the summation order — and with it the
+// bit-identity with k_clip_adam (adam_kernels.h), which is always 256 threads — holds at 256 threads only; every caller launches
+// 256 (replay.hip sample_impl, k_adam_pending), and the pair workgroups size their LDS for it (RB_ADAM_PAIR_T).
 // The arguments live in DEVICE memory (`ad`; the host rewrites them only when a pointer or a hyper-parameter changes):
 // by value they would occupy ~40 SGPRs of the hosting kernel on every path.  Pointers that come out of memory are generic
 // pointers — every access goes through a buffer descriptor instead (no flat instructions; 32-bit byte offsets: the caller
