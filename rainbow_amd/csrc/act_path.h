@@ -1,5 +1,5 @@
 // Agent.act / evaluate_q (agent.py:53-55, 110-112; main.py:153, test.py:26,39): the forward of ONE un-batched
-// state.  The training kernels (conv_lds.h, noisy_linear.h) are shaped for 96 images: with one image they run 2-3
+// state.  The training kernels (conv_fwd.h, noisy_linear.h) are shaped for 96 images: with one image they run 2-3
 // workgroups per layer and cost the same 14 us as with 96 (a pure staging-latency chain).  This path trades MFMA for
 // breadth instead: one output channel (conv) or one weight row per wave (noisy linear), hundreds of small
 // workgroups, weights read as wave-uniform scalars / one coalesced sweep, so a layer is one memory round trip.
@@ -8,6 +8,7 @@
 #include "noisy_linear.h"
 #include "rb_common.h"
 #include "rb_device.h"
+#include "kernel_stamp.h"
 
 #define RB_ACT_LDS 15360          // floats of input patch per workgroup (60 KB)
 #define RB_ACT_MAXPOS 128         // output positions per workgroup (two 64-lane passes)

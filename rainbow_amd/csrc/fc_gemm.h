@@ -30,6 +30,7 @@
 // the same input columns (the hidden layer; the output layer keeps noisy_linear.h).
 #pragma once
 #include "noisy_linear.h"
+#include "kernel_stamp.h"
 
 #define RB_TG_T 128
 #define RB_TG_KS 32

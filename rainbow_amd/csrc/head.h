@@ -1,6 +1,7 @@
 // head.h — the C51 head of the learn step (k_head) and of Agent.act (k_head_act).  Included by learner.hip only.
 #pragma once
 #include "learner_internal.h"
+#include "kernel_stamp.h"
 
 // ------------------------------------------------------------------------- head --
 // One workgroup per sample b.  Dueling combine (model.py:74-75), log-softmax of
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(RB_HEAD_THREADS) void k_head(int B, int Z, int A, c
                                                float delta_z, float* log_ps_a_out, float* pns_a_out, float* m_out,
                                                int32_t* a_star_out, float* loss_out, float* dlogits, long long* step_ctr,
                                                const int32_t* batch_status, int32_t* status_copy, float* dlogitsT, HeadTenants tn) {
-  // tenant workgroups behind the B samples: the conv input-gradient kernels' weight operand of THIS step (conv_lds.h
+  // tenant workgroups behind the B samples: the conv input-gradient kernels' weight operand of THIS step (conv_dx.h
   // rb_conv_wt_block) — independent of the head, on CUs this launch leaves idle (32 of 256 busy), two launches ahead of its
   // first reader
   if ((int)blockIdx.x >= B) {

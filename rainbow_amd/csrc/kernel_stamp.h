@@ -1,0 +1,26 @@
+// kernel_stamp.h — the in-kernel timestamps of the RB_STAMP / RB_STAMP_FINE diagnostic builds (tools/build_variant.sh): RB_CSTAMP
+// (one slot per phase of a launch's first / last workgroup, g_cstamp) and RB_WGT (the per-workgroup timeline, g_wgt); in the
+// product build every macro is ((void)0).  learner.hip defines the two arrays and reads them back.  Included directly by every
+// header whose kernels stamp: conv_fwd.h, conv_dx.h, conv_dw.h, fc_gemm.h, noisy_linear.h, head.h, act_path.h, and by learner.hip.
+#pragma once
+#include "rb_device.h"
+
+#if defined(RB_STAMP)
+extern __device__ long long g_cstamp[64];
+#define RB_CSTAMP(i) do { if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) g_cstamp[i] = wall_clock64(); } while (0)
+#define RB_CSTAMP_LAST(i) do { if (threadIdx.x == 0 && blockIdx.x == gridDim.x - 1 && blockIdx.y == gridDim.y - 1 && blockIdx.z == gridDim.z - 1) g_cstamp[i] = wall_clock64(); } while (0)
+// per-workgroup timeline: g_wgt[kernel id][workgroup][slot] = wall_clock64 (100 MHz) at phase boundaries, slot 7 = where
+// it ran (XCC id << 16 | HW_ID bits) — tools/wg_timeline.py draws the schedule of a launch from it
+#define RB_WGT_KERNELS 14
+#define RB_WGT_WGS 2048
+extern __device__ long long g_wgt[RB_WGT_KERNELS][RB_WGT_WGS][8];
+#define RB_WGT(kid, wg, slot) do { if (threadIdx.x == 0 && (wg) < RB_WGT_WGS) g_wgt[kid][wg][slot] = wall_clock64(); } while (0)
+#define RB_WGT_HW(kid, wg) do { if (threadIdx.x == 0 && (wg) < RB_WGT_WGS) g_wgt[kid][wg][7] = ((long long)__builtin_amdgcn_s_getreg(6164) << 16) | (__builtin_amdgcn_s_getreg(63492) & 0xffff); } while (0)
+#define RB_WGT_ROLE(kid, wg, role) do { if (threadIdx.x == 0 && (wg) < RB_WGT_WGS) g_wgt[kid][wg][1] = (role); } while (0)
+#else
+#define RB_WGT_ROLE(kid, wg, role) ((void)0)
+#define RB_CSTAMP(i) ((void)0)
+#define RB_CSTAMP_LAST(i) ((void)0)
+#define RB_WGT(kid, wg, slot) ((void)0)
+#define RB_WGT_HW(kid, wg) ((void)0)
+#endif

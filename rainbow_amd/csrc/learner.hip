@@ -5,7 +5,7 @@
 // Reference being replaced: model.py (NoisyLinear, DQN) and agent.py:61-98.  The reference
 // issues ~1750 framework ops per learn(); here the step is a fixed chain of 14 launches after the sampler
 // (DESIGN.md §3 has the table with what bounds each):
-//   conv fwd x L (conv_lds.h: operands in LDS, 8 waves split K)
+//   conv fwd x L (conv_fwd.h: operands in LDS, 8 waves split K)
 //   -> fc_h, fc_z forward (noisy_linear.h k_nl_fwd3: weights streamed once, whole K per block, no partials)
 //   -> head (dueling + softmaxes + double-Q + projection + loss + dlogits, one workgroup per sample, atom bins in LDS)
 //   -> fc_z backward (dW || dX in one launch) -> fc_h backward (dW || dX || the sum-tree priority write-back)
@@ -21,6 +21,7 @@
 //   optimizer_host.h / act_host.h / exchange_host.h / layout_api.h / launch_plan_debug.h   the other entry points, by concern
 // Each is included HERE and nowhere else (they define non-template kernels and static functions).
 #include "learner_internal.h"
+#include "kernel_stamp.h"
 #include "learner_plan.h"
 #include "noise_kernel.h"
 #include "grad_finish.h"
@@ -285,7 +286,7 @@ static int learn_impl(rb_learner_t* l, const ImgSrc& src, const uint8_t* states_
   int rc = forward(l, 2 * B, B, src, on, tg, stream);
   if (rc != RB_OK) return rc;
   {
-    // tenant workgroups of the head launch: the conv input-gradient kernels' weight operand of this step (conv_lds.h rb_conv_wt_block)
+    // tenant workgroups of the head launch: the conv input-gradient kernels' weight operand of this step (conv_dx.h rb_conv_wt_block)
     const HeadPlan hp = plan_head(plan_in(l));
     HeadTenants tn;
     memset(&tn, 0, sizeof(tn));

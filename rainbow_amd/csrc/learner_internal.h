@@ -2,7 +2,9 @@
 // declarations of the few host functions that are called across the files (learner.hip is ONE translation unit: the
 // headers below are its sections, each included exactly once — several of them define non-template kernels).
 #pragma once
-#include "conv_lds.h"
+#include "conv_fwd.h"
+#include "conv_dx.h"
+#include "conv_dw.h"
 #include "noise_body.h"
 #include "adam_body.h"
 #include "learner_problems.h"
@@ -194,7 +196,7 @@ struct rb_learner {
   unsigned* gemm_ctr;   // its per-tile arrival counters (self-resetting)
   float* dw_part[3];    // [ws_l][cout][K+1]
   float* conv_wT[3];    // layers >= 1: the input-gradient kernels' weight operand [S*S phases][cin / 32 tiles][kpad][32], rewritten
-                        // every step by tenant workgroups of the head launch (conv_lds.h rb_conv_wt_block); pad rows stay zero
+                        // every step by tenant workgroups of the head launch (conv_dx.h rb_conv_wt_block); pad rows stay zero
   float* log_ps_a;      // [B][Z]
   float* pns_a;         // [B][Z]
   float* m;             // [B][Z]

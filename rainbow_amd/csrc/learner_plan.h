@@ -58,14 +58,14 @@ static LearnerCaps plan_caps(const Layout& L, const RbOpts& opt) {
 }
 
 // --------------------------------------------------------------------- geometry --
-// The five conv geometries with the tile parameters of their forward kernels (conv_lds.h): NT 32-position tiles per workgroup,
+// The five conv geometries with the tile parameters of their forward kernels (conv_fwd.h): NT 32-position tiles per workgroup,
 // PR patch rows, KMAX reduction length staged, FIRST = reads frames, PCH output positions per workgroup.
 template <class G_, int NT_, int PR_, int KMAX_, bool FIRST_, int PCH_ = 32 * NT_>
 struct ConvCfg {
   using G = G_;
   static constexpr int NT = NT_, PR = PR_, KMAX = KMAX_, PCH = PCH_;
   static constexpr bool FIRST = FIRST_;
-  // whole-K 16x16x4 tiles, one wave per tile, no cross-wave reduction (conv_lds.h T16).  Every later layer of the canonical stack
+  // whole-K 16x16x4 tiles, one wave per tile, no cross-wave reduction (conv_fwd.h T16).  Every later layer of the canonical stack
   // qualifies (cin * KK == KMAX and cout % 32 == 0 by construction); the data-efficient ones do not (K % 16 != 0, 9 positions)
   static constexpr bool T16_OK = KMAX % 16 == 0 && (KMAX / G::KK) % 4 == 0 && 2 * ((PCH + 15) / 16) <= 16 && (PCH % 16 == 0 || PCH >= G::P) && G::P > 16;
 };
@@ -120,7 +120,7 @@ static ConvFwdPlan plan_conv_fwd_g(const PlanIn& in, int layer, int n_on, int n_
     return p;
   }
   const bool out_blocked = layer == in.L.nconv - 1 && in.caps.fast_fc;
-  // large batches: one round of workgroups, each keeping its weight slab for ipb images of one net (conv_lds.h)
+  // large batches: one round of workgroups, each keeping its weight slab for ipb images of one net (conv_fwd.h)
   const bool multi_forced = in.opt.conv_multi >= 0;
   int ipb = 0;
   if (multi_forced) ipb = in.opt.conv_multi;
@@ -164,7 +164,7 @@ static ConvFwdPlan plan_conv_fwd_g(const PlanIn& in, int layer, int n_on, int n_
     }
   }
   // split-K 32x32x2 tiles: first layers (above) and the data-efficient second layer; float states (act / evaluate) have an
-  // instantiation of their own (conv_lds.h F32SRC)
+  // instantiation of their own (conv_fwd.h F32SRC)
   p.kernel = (C::FIRST && f32) ? CONV_FWD_LDS_F32 : CONV_FWD_LDS; p.block = RB_CONV_THREADS;
   return p;
 }
@@ -173,7 +173,7 @@ static ConvFwdPlan plan_conv_fwd(const PlanIn& in, int layer, int n_on, int n_tg
 }
 
 // ---------------------------------------------------------- conv input gradient --
-// The data gradient of conv layer `layer` (>= 1) on the whole-K 16x16x4 tile kernel (conv_lds.h k_conv_dx_t16_multi): the image-loop
+// The data gradient of conv layer `layer` (>= 1) on the whole-K 16x16x4 tile kernel (conv_dx.h k_conv_dx_t16_multi): the image-loop
 // form, i.e. batches of 64 and more (or RB_OPTS dx_ipb > 1, the test hook), the canonical later layers' geometries (64 output
 // channels, kernel size a multiple of the stride); the data-efficient second layer's image loop is k_conv_dx_lds<..., MULTI>.
 // Decides the layout of conv_wT too (the head launch's tenant jobs write it).

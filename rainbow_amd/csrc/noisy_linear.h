@@ -21,6 +21,7 @@
 // K % 32 == 0, all leading dimensions and offsets multiples of 4 floats.
 #pragma once
 #include "rb_device.h"
+#include "kernel_stamp.h"
 #include "replay_internal.h"
 
 struct NlWeights {
@@ -31,11 +32,6 @@ struct NlWeights {
   const float* bmu;     // [N]
   const float* bsigma;  // [N]
 };
-
-// k-blocked activation layout consumed by k_nl_fwd: element (row, k) of a [rows][K] matrix
-__host__ __device__ inline int64_t rb_blocked_index(int row, int k, int rows) {
-  return ((int64_t)(k >> 4) * rows + row) * 16 + (k & 15);
-}
 
 // W = mu + sigma * (eo * ein), component-wise, three separately rounded operations
 __device__ __forceinline__ float4 rb_noisy4(float4 mu, float4 sg, float eo, float4 e) {
@@ -255,7 +251,7 @@ __global__ __launch_bounds__(64 * RB_NL_FWD_WAVES) void k_nl_fwd3(NlFwd2Args a) 
       if (a.relu) o = fmaxf(o, 0.0f);
       const int rowi = a.m_base[net] + m;
       a.out[(int64_t)rowi * a.ld_out + n] = o;
-      if (a.out_blocked) a.out_blocked[((int64_t)(n >> 4) * a.rows_total + rowi) * 16 + (n & 15)] = o;
+      if (a.out_blocked) a.out_blocked[rb_blocked_index(rowi, n, a.rows_total)] = o;
     }
   }
 }
