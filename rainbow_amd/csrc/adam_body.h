@@ -68,24 +68,52 @@ __device__ __forceinline__ void rb_adam_quad(float4& P, float4& G, float4& M, fl
 // The plain pass (no skipped range) as hosted workgroups: block `eb` of `nblk`.  The element loops work for any block size that
 // is a multiple of 64, but the prologue hands norm partial i to thread i % blockDim.x, so the summation order — and with it the
 // bit-identity with k_clip_adam (adam_kernels.h), which is always 256 threads — holds at 256 threads only; every caller launches
-// 256 (replay.hip sample_impl, k_adam_pending), and the pair workgroups size their LDS for it (RB_ADAM_PAIR_T).
-// The arguments live in DEVICE memory (`ad`; the host rewrites them only when a pointer or a hyper-parameter changes):
-// by value they would occupy ~40 SGPRs of the hosting kernel on every path.  Pointers that come out of memory are generic
+// 256 (replay.hip sample_impl, k_adam_pending).
+// The arguments live in DEVICE memory (`ad`; the host rewrites them only when a pointer or a hyper-parameter changes, with
+// k_store_adam_args in a launch of its own): by value they would occupy ~50 SGPRs of the hosting kernel on every path.  They are
+// read through the SCALAR path (rb_ld_uniform), so every field is wave-uniform to the compiler: fetched with vector loads the
+// pointers sat in VGPRs, every buffer descriptor was "divergent", and each load and store of the pass was wrapped in a
+// waterfall loop (4 v_readfirstlane, two compares, s_and_saveexec, the access, a branch: 350 readfirstlanes and 91 loops in
+// the hosted region of the sampler kernel, profiles/hosted_pass_isa.txt).  Pointers that come out of memory are generic
 // pointers — every access goes through a buffer descriptor instead (no flat instructions; 32-bit byte offsets: the caller
 // guarantees 4 n < 2^31).  Requires a.step_dev (the step number cannot be a launch-time scalar here).
-// everything between a hosted workgroup's first loads and its update: batch status, the norm from the partial list (fixed
-// order), the bias corrections from the device step counter.  Returns false when the update is to be skipped.
-__device__ __forceinline__ bool rb_adam_hosted_prologue(ClipAdamArgs& a, int eb, unsigned st_lo, unsigned st_hi, float* s_red16, float* coef_out) {
+//
+// ONE memory trip per workgroup.  Everything a workgroup reads is requested before its first wait, earliest-consumed first
+// (vmcnt retires in order): the batch status, the step number, the thread's first 16 norm partials (rb_adam_hosted_request),
+// the pair workgroups' noise factors, then the p / g / m / v quads.  The status branch, the partial sum, rb_block_sum's two
+// barriers and the bias corrections then run while the quads are in flight (before, the status word was loaded BEHIND the
+// quads and its wait drained them, and only then were the partials requested: three dependent trips per pair workgroup).
+struct rb_adam_req {
+  float status;                // raw bits of *batch_status (0 without one)
+  unsigned st_lo, st_hi;       // the step number's halves
+  float pv[16];                // partials threadIdx.x + u * blockDim.x (clamped to the last one)
+};
+__device__ __forceinline__ void rb_adam_hosted_request(const ClipAdamArgs& a, rb_adam_req& q) {
   const unsigned T = blockDim.x;
-  if (a.batch_status && __builtin_bit_cast(int, rb_ld1_buf(rb_make_buf(a.batch_status), 0, 0)) != 0) {   // block-uniform
-    if (eb == 0 && threadIdx.x == 0 && a.norm_out) rb_st1_wt(a.norm_out, 0, 0.0f);
-    return false;
+  q.status = 0.0f;
+  if (a.batch_status) q.status = rb_ld1_buf(rb_make_buf(a.batch_status), 0, 0);     // (uniform branch; every lane, one address)
+  const rb_buf bs = rb_make_buf(a.step_dev);                                        // (every lane: no divergent branch between the loads)
+  q.st_lo = __builtin_bit_cast(unsigned, rb_ld1_buf(bs, 0, 0)); q.st_hi = __builtin_bit_cast(unsigned, rb_ld1_buf(bs, 4, 0));
+  const rb_buf bpart = rb_make_buf(a.part);
+#pragma unroll
+  for (int u = 0; u < 16; ++u) {
+    const int i = (int)threadIdx.x + u * (int)T;
+    q.pv[u] = rb_ld1_buf(bpart, 4u * (unsigned)(i < a.nparts ? i : a.nparts - 1), 0);
   }
+}
+// everything between a hosted workgroup's loads and its update: batch status, the norm from the partial list (fixed order:
+// thread t adds partials t, t + T, t + 2 T, ... in index order, then rb_block_sum), the bias corrections from the device step
+// counter.  Returns false when the update is to be skipped.
+__device__ __forceinline__ bool rb_adam_hosted_prologue(ClipAdamArgs& a, int eb, const rb_adam_req& q, float* s_red16, float* coef_out) {
+  const unsigned T = blockDim.x;
   float acc = 0.0f;
+#pragma unroll
+  for (int u = 0; u < 16; ++u)
+    if ((int)threadIdx.x + u * (int)T < a.nparts) acc += q.pv[u];
   {
-    // 16 partials in flight per trip, added in index order (a loop of single loads is one L2 round trip per iteration)
+    // lists beyond 16 T partials: 16 in flight per further trip (a loop of single loads is one L2 round trip per iteration)
     const rb_buf bpart = rb_make_buf(a.part);
-    for (int i0 = (int)threadIdx.x; i0 < a.nparts; i0 += 16 * (int)T) {
+    for (int i0 = (int)threadIdx.x + 16 * (int)T; i0 < a.nparts; i0 += 16 * (int)T) {
       float pv[16];
 #pragma unroll
       for (int u = 0; u < 16; ++u) {
@@ -98,12 +126,18 @@ __device__ __forceinline__ bool rb_adam_hosted_prologue(ClipAdamArgs& a, int eb,
     }
   }
   if (threadIdx.x == 0) {
-    const double t = (double)(long long)(((unsigned long long)st_hi << 32) | st_lo);
+    const double t = (double)(long long)(((unsigned long long)q.st_hi << 32) | q.st_lo);
     const double bc1 = 1.0 - pow(a.beta1, t), bc2 = 1.0 - pow(a.beta2, t);
     s_red16[16] = (float)(-(a.lr / bc1));
     s_red16[17] = (float)sqrt(bc2);
   }
   acc = rb_block_sum(acc, s_red16);
+  // the status branch BEHIND the sum (a skipped update is the rare case and may pay for a sum it drops): in front of it the
+  // compiler sank the partial loads into the branch's far side, behind the status word's round trip
+  if (rb_wave_uniform(__builtin_bit_cast(int, q.status)) != 0) {   // block-uniform
+    if (eb == 0 && threadIdx.x == 0 && a.norm_out) rb_st1_wt(a.norm_out, 0, 0.0f);
+    return false;
+  }
   const float total = sqrtf(acc);
   float coef = a.max_norm / (total + 1e-6f);
   if (coef > 1.0f) coef = 1.0f;                                    // clamp(max=1.0)
@@ -114,41 +148,27 @@ __device__ __forceinline__ bool rb_adam_hosted_prologue(ClipAdamArgs& a, int eb,
   return true;
 }
 
-// pair workgroup `pb` (0-based among the pair workgroups): 2 (mu, sigma) quad pairs per thread = 14 data quads in flight.
-// The noise products eps_out * eps_in of a thread's pairs are requested FIRST, parked in LDS (8 KB per 256-thread workgroup)
-// while the data loads and the prologue are in flight, and read back for the update: as registers they pushed the hosting
-// sampler kernel over its 128-register budget (5 spilled VGPRs, a scratch segment: +10 us per step for EVERY kernel), and with
-// one pair per thread the pass streamed too thinly to gain anything (38.8 against 36.3 us for the hosting launch).
-#define RB_ADAM_PAIR_T 256            // hosted workgroups are 256 threads (replay.hip sample_impl, adam_kernels.h k_adam_pending)
+// pair workgroup `pb` (0-based among the pair workgroups): 2 (mu, sigma) quad pairs per thread = 14 data quads in flight, behind
+// the prologue's requests and the noise factors eps_out / eps_in of the thread's pairs (10 registers; their products are formed
+// when the update needs them.  With one pair per thread the pass streamed too thinly to gain anything: 38.8 against 36.3 us
+// for the hosting launch).
 __device__ __forceinline__ void rb_adam_hosted_pairs(ClipAdamArgs& a, int eb, int pb, float* s_red16) {
   constexpr int PU = 2;
-  __shared__ float4 s_prod[PU * RB_ADAM_PAIR_T];
   const unsigned T = blockDim.x;
   const unsigned len4 = (unsigned)a.pair_len4, mu4 = (unsigned)a.pair_mu4;
   const unsigned base = (unsigned)pb * (T * PU) + threadIdx.x;
-  unsigned st_lo = 0, st_hi = 0;
-  if (threadIdx.x == 0) {
-    const rb_buf bs = rb_make_buf(a.step_dev);
-    st_lo = __builtin_bit_cast(unsigned, rb_ld1_buf(bs, 0, 0)); st_hi = __builtin_bit_cast(unsigned, rb_ld1_buf(bs, 4, 0));
-  }
-  {
-    const rb_buf beo = rb_make_buf(a.pair_eout), bei = rb_make_buf(a.pair_ein);
-    float4 E[PU];
-    float eo[PU];
+  rb_adam_req q;
+  rb_adam_hosted_request(a, q);
+  const rb_buf beo = rb_make_buf(a.pair_eout), bei = rb_make_buf(a.pair_ein);
+  float4 E[PU];
+  float eo[PU];
 #pragma unroll
-    for (int u = 0; u < PU; ++u) {
-      unsigned j = base + u * T;
-      if (j >= len4) j = len4 - 1;
-      const unsigned row = j / (unsigned)a.pair_f4, cq = j - row * (unsigned)a.pair_f4;
-      eo[u] = rb_ld1_buf(beo, 4 * row, 0);
-      E[u] = rb_ld4_buf(bei, 16 * (cq + ((int)row >= a.pair_split_row ? (unsigned)a.pair_f4 : 0u)), 0);
-    }
-#pragma unroll
-    for (int u = 0; u < PU; ++u) {                       // eps_out * eps_in: the inner product of the backward's g_mu * (eo * e)
-      float4 pr;
-      pr.x = eo[u] * E[u].x; pr.y = eo[u] * E[u].y; pr.z = eo[u] * E[u].z; pr.w = eo[u] * E[u].w;
-      s_prod[u * RB_ADAM_PAIR_T + threadIdx.x] = pr;
-    }
+  for (int u = 0; u < PU; ++u) {
+    unsigned j = base + u * T;
+    if (j >= len4) j = len4 - 1;
+    const unsigned row = j / (unsigned)a.pair_f4, cq = j - row * (unsigned)a.pair_f4;
+    eo[u] = rb_ld1_buf(beo, 4 * row, 0);
+    E[u] = rb_ld4_buf(bei, 16 * (cq + ((int)row >= a.pair_split_row ? (unsigned)a.pair_f4 : 0u)), 0);
   }
   const rb_buf bp = rb_make_buf(a.p), bg = rb_make_buf(a.g), bm = rb_make_buf(a.m), bv = rb_make_buf(a.v);
   float4 P[PU], G[PU], M[PU], V[PU], P2[PU], M2[PU], V2[PU];
@@ -162,14 +182,15 @@ __device__ __forceinline__ void rb_adam_hosted_pairs(ClipAdamArgs& a, int eb, in
     P2[u] = rb_ld4_buf(bp, 16 * i2, 0); M2[u] = rb_ld4_buf(bm, 16 * i2, 0); V2[u] = rb_ld4_buf(bv, 16 * i2, 0);
   }
   float coef;
-  if (!rb_adam_hosted_prologue(a, eb, st_lo, st_hi, s_red16, &coef)) return;
+  if (!rb_adam_hosted_prologue(a, eb, q, s_red16, &coef)) return;
   if (pb == 0 && threadIdx.x == 0 && a.pair_clipped) rb_st1_wt(reinterpret_cast<float*>(a.pair_clipped), 0, __builtin_bit_cast(float, coef < 1.0f ? 1 : 0));
 #pragma unroll
   for (int u = 0; u < PU; ++u) {
     const unsigned j = base + u * T;
     if (j >= len4) continue;
     const unsigned i = mu4 + j, i2 = i + len4;
-    const float4 pr = s_prod[u * RB_ADAM_PAIR_T + threadIdx.x];   // (each thread reads back its own entries: no barrier needed)
+    float4 pr;                                           // eps_out * eps_in: the inner product of the backward's g_mu * (eo * e)
+    pr.x = eo[u] * E[u].x; pr.y = eo[u] * E[u].y; pr.z = eo[u] * E[u].z; pr.w = eo[u] * E[u].w;
     float4 G2;                                           // the backward's own expression: g_sigma = g_mu * (eps_out * eps_in)
     G2.x = G[u].x * pr.x; G2.y = G[u].y * pr.y; G2.z = G[u].z * pr.z; G2.w = G[u].w * pr.w;
     rb_adam_quad(P[u], G[u], M[u], V[u], coef, a);
@@ -182,15 +203,12 @@ __device__ __forceinline__ void rb_adam_hosted_pairs(ClipAdamArgs& a, int eb, in
 
 template <int UNROLL>
 __device__ __forceinline__ void rb_adam_hosted_block(const ClipAdamArgs* ad, int eb, int nblk, float* s_red16 /* [18] */) {
-  // (the branch is decided from two words; each role then reads the argument fields IT uses: the whole struct live on both
-  // paths cost the hosting sampler kernel 18 spilled VGPRs and a scratch segment, and the whole step 10 us)
-  const int nplain = ad->hole4 > 0 ? ad->pair_blk0 : nblk;
+  ClipAdamArgs a = rb_ld_uniform(ad);                    // SGPRs; each role keeps only the fields it uses
+  const int nplain = a.hole4 > 0 ? a.pair_blk0 : nblk;
   if (eb >= nplain) {                                    // block-uniform: a (mu, sigma) pair workgroup
-    ClipAdamArgs ap = *ad;
-    rb_adam_hosted_pairs(ap, eb, eb - nplain, s_red16);
+    rb_adam_hosted_pairs(a, eb, eb - nplain, s_red16);
     return;
   }
-  ClipAdamArgs a = *ad;
   const unsigned T = blockDim.x;
   const unsigned n4 = (unsigned)(a.n >> 2);
   const unsigned hole_lo = a.hole4 > 0 ? a.hole_lo4 : n4, hole = a.hole4;
@@ -198,13 +216,8 @@ __device__ __forceinline__ void rb_adam_hosted_block(const ClipAdamArgs* ad, int
   auto real_of = [&](unsigned j) { return j < hole_lo ? j : j + hole; };
   const unsigned base = (unsigned)eb * (T * UNROLL) + threadIdx.x;
   const rb_buf bp = rb_make_buf(a.p), bg = rb_make_buf(a.g), bm = rb_make_buf(a.m), bv = rb_make_buf(a.v);
-  // the step number first (one lane): its bias corrections — two double pow — are formed while the block's parameter loads
-  // are in flight, not behind the norm's barrier
-  unsigned st_lo = 0, st_hi = 0;
-  if (threadIdx.x == 0) {
-    const rb_buf bs = rb_make_buf(a.step_dev);
-    st_lo = __builtin_bit_cast(unsigned, rb_ld1_buf(bs, 0, 0)); st_hi = __builtin_bit_cast(unsigned, rb_ld1_buf(bs, 4, 0));
-  }
+  rb_adam_req q;
+  rb_adam_hosted_request(a, q);
   float4 P[UNROLL], G[UNROLL], M[UNROLL], V[UNROLL];
 #pragma unroll
   for (int u = 0; u < UNROLL; ++u) {
@@ -215,7 +228,7 @@ __device__ __forceinline__ void rb_adam_hosted_block(const ClipAdamArgs* ad, int
     M[u] = rb_ld4_buf(bm, 16 * i, 0); V[u] = rb_ld4_buf(bv, 16 * i, 0);
   }
   float coef;
-  if (!rb_adam_hosted_prologue(a, eb, st_lo, st_hi, s_red16, &coef)) return;
+  if (!rb_adam_hosted_prologue(a, eb, q, s_red16, &coef)) return;
 #pragma unroll
   for (int u = 0; u < UNROLL; ++u) {
     const unsigned j = base + u * T;

@@ -156,6 +156,54 @@ int rb_learner_pending_launched(rb_learner_t* l) {
   l->adam_pending = 0;
   return RB_OK;
 }
+// TESTS ONLY (not declared in rainbow_hip.h): one optimiser pass over caller-owned buffers of ANY length.  The learner's own
+// flat buffers are padded to whole quads and never shorter than a block, so the n % 4 tail, a last block of clamped loads and
+// a pair range that ends inside a workgroup are reached only this way.  form 0: k_clip_adam<4, true, false> with the step by
+// value (the reference form); form 1: the hosted body as k_adam_pending, its arguments stored to `args_dev` (256 bytes) first,
+// the step read from `step_dev`.  `part` holds `nparts` > 0 partial sums of squares.  pair_len4 > 0 (form 1 only): quads
+// [pair_mu4, pair_mu4 + pair_len4) are a layer's mu weights, the pair_len4 quads behind them its sigma weights, whose gradient
+// the pass forms from pair_eout [rows] and pair_ein [2][4 * pair_f4] (ClipAdamArgs, adam_body.h).
+int rb_debug_adam_pass(int32_t form, float* p, float* g, float* m, float* v, int64_t n, const float* part, int32_t nparts,
+                       float max_norm, float* norm_out, const long long* step_dev, int64_t step, double lr, double beta1,
+                       double beta2, double eps, const int32_t* batch_status, int64_t pair_mu4, int64_t pair_len4, int32_t pair_f4,
+                       int32_t pair_split_row, const float* pair_eout, const float* pair_ein, int32_t* pair_clipped, void* args_dev,
+                       rb_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RB_REQUIRE(p && g && m && v && part && n >= 0 && n * 4 < (int64_t)0x7fffffff && nparts > 0, "rb_debug_adam_pass: bad buffers");
+  RB_REQUIRE(form == 0 ? (step >= 1 && pair_len4 == 0) : (form == 1 && step_dev && args_dev), "rb_debug_adam_pass: bad form");
+  static_assert(sizeof(ClipAdamArgs) <= 256, "rb_debug_adam_pass: args_dev is documented as 256 bytes");
+  ClipAdamArgs a;
+  memset(&a, 0, sizeof(a));
+  a.p = p; a.g = g; a.m = m; a.v = v; a.n = n;
+  a.part = part; a.nparts = nparts; a.max_norm = max_norm; a.norm_out = norm_out;
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  a.w1 = (float)(1.0 - beta1); a.b2 = (float)beta2; a.w2 = (float)(1.0 - beta2);
+  a.neg_step_size = (float)(-(lr / bc1)); a.bc2_sqrt = (float)sqrt(bc2); a.eps = (float)eps;
+  a.step_dev = form == 1 ? step_dev : nullptr; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2;
+  a.batch_status = batch_status;
+  const int64_t n4 = n >> 2;
+  unsigned grid = (unsigned)rb_div_up(n4 > 0 ? n4 : 1, 256 * 4);
+  if (form == 0) {
+    FusedDwAdamArgs f;
+    memset(&f, 0, sizeof(f));
+    RB_LAUNCH((k_clip_adam<4, true, false>), dim3(grid), dim3(256), stream, a, f);
+    RB_LAUNCH_CHECK();
+    return RB_OK;
+  }
+  if (pair_len4 > 0) {
+    RB_REQUIRE(pair_mu4 >= 0 && pair_mu4 + 2 * pair_len4 <= n4 && pair_f4 > 0 && pair_len4 % pair_f4 == 0 && pair_eout && pair_ein,
+               "rb_debug_adam_pass: bad pair range");
+    a.pair_mu4 = pair_mu4; a.pair_len4 = pair_len4; a.pair_f4 = pair_f4; a.pair_split_row = pair_split_row;
+    a.pair_eout = pair_eout; a.pair_ein = pair_ein; a.pair_clipped = pair_clipped;
+    a.hole_lo4 = (unsigned)pair_mu4; a.hole4 = (unsigned)(2 * pair_len4);
+    a.pair_blk0 = (int)rb_div_up(n4 - 2 * pair_len4 > 0 ? n4 - 2 * pair_len4 : 1, 256 * 4);
+    grid = (unsigned)(a.pair_blk0 + rb_div_up(pair_len4, 256 * 2));
+  }
+  RB_LAUNCH(k_store_adam_args, dim3(1), dim3(64), stream, a, reinterpret_cast<ClipAdamArgs*>(args_dev));
+  RB_LAUNCH_CHECK();
+  return rb_launch_adam_pending(reinterpret_cast<const ClipAdamArgs*>(args_dev), (int)grid, stream);
+}
+
 // rb_learner_clip_adam that leaves the pass pending when the handle's flags say so (RB_LEARNER_DEFER_UPDATE) and it can
 // (step = 0 with a device step counter, norm partials from the learn call); otherwise exactly rb_learner_clip_adam.
 int rb_learner_clip_adam_deferred(rb_learner_t* l, float max_norm, float* exp_avg, float* exp_avg_sq, double lr, double beta1,

@@ -318,6 +318,25 @@ __device__ __forceinline__ int rb_wave_uniform(int v) {
 #endif
 }
 
+// A whole argument struct out of device memory through the SCALAR path (constant address space: s_load into SGPRs), for a
+// struct the CALLER knows to be read-only while the kernel runs (written by an earlier launch) and whose address is
+// wave-uniform.  Every field is then uniform to the compiler: a pointer fetched with a vector load sits in VGPRs, and each
+// buffer access through it is wrapped in a waterfall loop.  sizeof(T) must be a multiple of 4.
+template <typename T>
+__device__ __forceinline__ T rb_ld_uniform(const T* p) {
+#if defined(RB_HOST_INTERP)
+  return *p;
+#else
+  static_assert(sizeof(T) % 4 == 0, "rb_ld_uniform: whole words only");
+  struct Words { unsigned w[sizeof(T) / 4]; };
+  const __attribute__((address_space(4))) unsigned* q = (const __attribute__((address_space(4))) unsigned*)(p);
+  Words t;
+#pragma unroll
+  for (unsigned i = 0; i < sizeof(T) / 4; ++i) t.w[i] = q[i];
+  return __builtin_bit_cast(T, t);
+#endif
+}
+
 // Ordering point for LDS traffic that stays inside one wave (a lane reads what another lane of the SAME wave wrote):
 // the hardware executes a wave's LDS operations in order, so no s_barrier is needed — this only pins the compiler's
 // (and the host interpreter's) ordering.
