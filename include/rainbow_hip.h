@@ -416,6 +416,31 @@ int rb_replay_update_sample(rb_replay_t* r, const int64_t* upd_tree_idx_dev, con
                             int64_t* actions_dev, float* returns_dev, float* nonterminals_dev,
                             float* weights_dev, rb_stream_t stream);
 
+/* Random-shift augmentation (DrQ, DrQ-eps, SPR) where the stacks are built.  The frame stacks of the LAST draw on this handle
+ * (rb_replay_sample* / rb_replay_update_sample called with states_dev = next_states_dev = NULL: the draw leaves its window table
+ * behind), each stack shifted by (dy, dx) in [-pad, pad] with edge replication — the 84 x 84 stack padded by `pad` pixels of its
+ * border and cropped at a random offset:
+ *     out[i][w][c][y][x] = frame[clamp(y + dy)][clamp(x + dx)],  clamp onto [0, 83],  w = 0 state / 1 next state,
+ * with ONE (dy, dx) for all `history` frames c of a stack and independent ones for the state and the next state of a sample.  A
+ * blanked frame stays 7056 zero bytes.  pad = 0 gives exactly the bytes rb_replay_sample writes when it is handed stack pointers.
+ *   shifts_in_dev != NULL: the shifts are read from there, int8 [batch][2][2] = [i][w] -> (dy, dx), clamped to [-pad, pad]
+ *                          (the parity hook of the tests);
+ *   shifts_in_dev == NULL: Philox4x32-10 with key = seed ^ 0x5348494654 (seed: rb_replay_create's) and counter (hi = draw, lo = i):
+ *                          words 0, 1 are the state's (dy, dx), words 2, 3 the next state's, each (int)((word * (2 pad + 1)) >> 32)
+ *                          - pad.  `draw` is the caller's batch counter (increment it per batch).  The tagged key keeps these
+ *                          draws off the sampler's stream (key = seed, counter (rng_counter + attempt, i)); the device header and
+ *                          its rng_counter are neither read nor written.
+ *   shifts_out_dev != NULL: receives the shifts actually used, same [batch][2][2] layout.
+ * states_dev / next_states_dev: u8[batch][history][7056], 16-byte aligned; batch in [1, 1024], pad in [0, 8].  Reads the replay
+ * only (it is no mutation and draws nothing); an early draw in flight is joined first, as by every entry point outside a draw.
+ * After a draw that gave up (last_status = 1) the windows of that draw are gathered, as rb_replay_sample's own gather does.
+ * The validation view (rb_replay_state_at / rb_replay_states_at) is never shifted.                                          */
+int rb_replay_gather_shifted(rb_replay_t* r, int32_t batch, int32_t pad, uint64_t draw,
+                             const int8_t* shifts_in_dev,   /* NULL: device Philox */
+                             uint8_t* states_dev, uint8_t* next_states_dev,
+                             int8_t* shifts_out_dev,        /* may be NULL */
+                             rb_stream_t stream);
+
 /* ReplayMemory.__next__ (memory.py:167-178): blanked history stack for data index i,
  * as f32 /255, out_dev f32[history][7056].  With S streams: slots i - (history-1-t) S, t = 0..history-1. */
 int rb_replay_state_at(rb_replay_t* r, int64_t data_index, float* out_dev, rb_stream_t stream);

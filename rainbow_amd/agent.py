@@ -593,7 +593,10 @@ class Agent:
         stream = self._stream()                       # ONE lookup per step (torch.cuda.current_stream costs ~4 us a call)
         if self._zero_copy_ok is None:                # a property of the learner's configuration: asked once
             self._zero_copy_ok = bool(self._lib.rb_learner_zero_copy_ok(self._h))
-        zero_copy = device_mem and self._zero_copy_ok and mem.history == self._cfg.history and mem.n == self.n
+        # (a memory with random-shift augmentation — ReplayMemory augment_pad — builds shifted stacks in its gather: the ring
+        # holds the un-shifted frames, so the step takes the gathered path)
+        zero_copy = (device_mem and self._zero_copy_ok and mem.history == self._cfg.history and mem.n == self.n
+                     and not getattr(mem, "augment_pad", 0))
         lib_comm = self._exchange is not None and getattr(self._exchange, "comm", None) is not None
         if (zero_copy and self._one_call and _target_raw_normals is None and _unit_uniforms is None and self._fuse_update
                 and ((self._exchange is None and not self._dist) or lib_comm)

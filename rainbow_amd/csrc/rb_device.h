@@ -191,6 +191,16 @@ __device__ __forceinline__ unsigned rb_ldg_u32(const void* p) {
 #endif
 }
 
+// v_alignbyte_b32: the 32 bits of the 64-bit pair {hi, lo} that start at byte `shift & 3` of lo — four bytes at any byte offset
+// out of two adjacent dwords in one VALU instruction (shift 0 returns lo: hi contributes nothing).
+__device__ __forceinline__ uint32_t rb_alignbyte(uint32_t hi, uint32_t lo, unsigned shift) {
+#if defined(RB_HOST_INTERP)
+  return (uint32_t)(((((uint64_t)hi) << 32) | (uint64_t)lo) >> (8u * (shift & 3u)));
+#else
+  return __builtin_amdgcn_alignbyte(hi, lo, shift);
+#endif
+}
+
 // 16-byte global/LDS accesses (pointers must be 16-byte aligned)
 __device__ __forceinline__ float4 rb_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void rb_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }

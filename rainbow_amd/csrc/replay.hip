@@ -20,6 +20,7 @@
 #include "replay_append.h"
 #include "replay_spec.h"
 #include "replay_sample.h"
+#include "replay_shift.h"
 #include "replay_view.h"
 
 #include <stdlib.h>
@@ -604,6 +605,26 @@ int rb_replay_update_sample(rb_replay_t* r, const int64_t* upd_tree_idx_dev, con
               returns_dev, nonterminals_dev, weights_dev, r->fail_host, (SpecResult*)nullptr, 0u);
   RB_LAUNCH_CHECK();
   return launch_gather(v, batch, r->win, states_dev, next_states_dev, stream);
+}
+
+// The frame stacks of the LAST draw on the handle with random-shift augmentation (replay_shift.h): reads the window table that draw
+// wrote, the ring and nothing else — no mutation of the replay, the header (rng_counter included) untouched.  After a draw that gave
+// up the table holds that draw's windows and they are gathered, as rb_replay_sample's own gather does.
+int rb_replay_gather_shifted(rb_replay_t* r, int32_t batch, int32_t pad, uint64_t draw, const int8_t* shifts_in_dev,
+                             uint8_t* states_dev, uint8_t* next_states_dev, int8_t* shifts_out_dev, rb_stream_t stream) {
+  RB_REQUIRE(r != nullptr, "rb_replay_gather_shifted: NULL handle");
+  RB_REQUIRE(states_dev != nullptr, "rb_replay_gather_shifted: states_dev is NULL");
+  RB_REQUIRE(next_states_dev != nullptr, "rb_replay_gather_shifted: next_states_dev is NULL");
+  RB_REQUIRE(batch >= 1 && batch <= r->max_batch, "rb_replay_gather_shifted: batch must be in [1,%d], got %d", r->max_batch, (int)batch);
+  RB_REQUIRE(pad >= 0 && pad <= RB_SHIFT_MAX_PAD, "rb_replay_gather_shifted: pad must be in [0,%d], got %d", RB_SHIFT_MAX_PAD, (int)pad);
+  RB_REQUIRE((((uintptr_t)states_dev | (uintptr_t)next_states_dev) & 15u) == 0,
+             "rb_replay_gather_shifted: states_dev and next_states_dev must be 16-byte aligned");
+  RB_SPEC_JOIN(r);
+  RB_LAUNCH_T("sample:k_gather_stacks_shift", k_gather_stacks_shift, dim3((unsigned)(batch * 2 * r->history)), dim3(256), stream, view_of(r),
+              batch, win_of(r, r->win_sel), pad, r->seed ^ RB_SHIFT_KEY_TAG, draw, shifts_in_dev, states_dev, next_states_dev,
+              shifts_out_dev);
+  RB_LAUNCH_CHECK();
+  return RB_OK;
 }
 
 // ------------------------------------------------------------- validation view --

@@ -15,6 +15,11 @@ Vectorised environments: `ReplayMemory(args, capacity, streams=S)` holds S inter
 one sum tree (stream s owns the slots s, s + S, s + 2S, ...) and is filled a round at a time with `append_streams` — one
 transition per environment, one launch.  Sampling, priorities and IS weights are those of ONE replay over all streams; windows
 and n-step returns never cross from one stream into another.  streams=1 is the reference's replay, unchanged.
+
+Random-shift augmentation (DrQ): `args.augment_pad = p` (1..8; absent or 0 = off, today's launches exactly) shifts every sampled
+stack by (dy, dx) in [-p, p] with edge replication — `states` and `next_states` independently, all `history` frames of one stack
+alike — inside the frame-stack gather (rb_replay_gather_shifted).  Only `sample_device(gather=True)` and `sample()` are shifted;
+`__next__`, `state_at` / `states_at` (validation, evaluation) never are.
 """
 import ctypes as C
 import os
@@ -76,6 +81,9 @@ class ReplayMemory:
     _stage = None
     _handle = None
     streams = 1                 # (a pickle written before interleaved streams existed restores as one stream)
+    augment_pad = 0             # (a pickle written before the random-shift option existed restores with it off)
+    _aug_draw = 0               # batches shifted so far: the `draw` word of the shift RNG's counter (rb_replay_gather_shifted)
+    MAX_AUGMENT_PAD = 8
     _lazy = os.environ.get("RAINBOW_AMD_LAZY_PRIORITIES", "1") != "0"
 
     @property
@@ -111,6 +119,8 @@ class ReplayMemory:
         self.streams = int(streams)
         self.stream_t = np.zeros(self.streams, dtype=np.int32)  # the same counter per environment stream (append_streams)
         self._seed = int(seed if seed is not None else np.random.randint(0, 2 ** 31 - 1))
+        self.augment_pad = self._checked_pad(getattr(args, "augment_pad", 0))
+        self._aug_draw = 0
         self._lazy = os.environ.get("RAINBOW_AMD_LAZY_PRIORITIES", "1") != "0"
         self._pending = None
         self._stage = {}
@@ -120,6 +130,13 @@ class ReplayMemory:
         self._ptr_cache = {}
         self.current_idx = 0
         self._init_beta_source()
+
+    @classmethod
+    def _checked_pad(cls, pad):
+        pad = int(pad or 0)
+        if not 0 <= pad <= cls.MAX_AUGMENT_PAD:
+            raise ValueError("ReplayMemory: augment_pad must be in [0, %d], got %d" % (cls.MAX_AUGMENT_PAD, pad))
+        return pad
 
     def _create(self):
         self._h = C.c_void_p()
@@ -335,12 +352,18 @@ class ReplayMemory:
             L.check(self._lib, self._lib.rb_replay_buffers(self._h, C.byref(self._bufs)))
         return self._bufs.frames_dev, self._bufs.window_dev, int(self._bufs.window_len)
 
-    def sample_device(self, batch_size, unit_uniforms=None, gather=True, noise_job=None, stream=None):
+    def sample_device(self, batch_size, unit_uniforms=None, gather=True, noise_job=None, stream=None, shifts=None):
         """Device-resident batch: dict(tree_idxs i64[B], states u8[B,h,84,84], next_states u8, actions i64[B],
         returns f32[B], nonterminals f32[B], weights f32[B]).  Asynchronous.  unit_uniforms (float64 device
         tensor [attempts,B]) injects the sampler's random numbers for parity tests.  gather=False skips the
         frame-stack copies (states/next_states are then stale): the consumer reads the ring via frame_source().
-        noise_job (rainbow_amd._lib.NoiseJob from the learner) lets the launch also carry the noise resample."""
+        noise_job (rainbow_amd._lib.NoiseJob from the learner) lets the launch also carry the noise resample.
+        With augment_pad > 0 and gather=True the stacks come out of the shifted gather (one launch behind the sampler's, which
+        then builds no stacks itself) and the dict also holds `shifts` (int8 [B,2,2]: [i][state, next] -> (dy, dx), the shifts
+        used).  `shifts` (int8 [B,2,2]) injects them for parity tests; otherwise they are the device draw number `_aug_draw`,
+        which every augmented batch advances by one."""
+        if self.augment_pad and gather:
+            return self._sample_device_shifted(batch_size, unit_uniforms, noise_job, stream, shifts)
         o = self._buffers(batch_size)
         if float(self.priority_weight) != self._neg_beta_val and not torch.cuda.is_current_stream_capturing():
             self._sync_beta()
@@ -374,6 +397,29 @@ class ReplayMemory:
             rc = self._lib.rb_replay_sample(self._handle, key[0], float(self.priority_weight), uu_ptr, attempts, *ptrs, stream)
         if rc != 0:
             L.check(self._lib, rc)
+        return o
+
+    def _sample_device_shifted(self, batch_size, unit_uniforms, noise_job, stream, shifts):
+        """sample_device(gather=True) under augment_pad > 0: the draw with NULL stacks (gather=False: the same three-way choice of
+        launch, update and noise fusions as they are), then the shifted gather of that draw's window table."""
+        if stream is None:
+            stream = self._stream()
+        o = self.sample_device(batch_size, unit_uniforms, gather=False, noise_job=noise_job, stream=stream)
+        B = int(batch_size)
+        sh = o.get("shifts")
+        if sh is None:
+            sh = o["shifts"] = torch.zeros(B, 2, 2, dtype=torch.int8, device=self.device)
+        in_ptr = None
+        if shifts is not None:
+            self._shifts_in = torch.as_tensor(shifts).to(device=self.device, dtype=torch.int8).contiguous()
+            if tuple(self._shifts_in.shape) != (B, 2, 2):
+                raise ValueError("sample_device: shifts must be [%d, 2, 2], got %s" % (B, tuple(self._shifts_in.shape)))
+            in_ptr = self._shifts_in.data_ptr()
+        rc = self._lib.rb_replay_gather_shifted(self._handle, B, int(self.augment_pad), int(self._aug_draw), in_ptr,
+                                                o["states"].data_ptr(), o["next_states"].data_ptr(), sh.data_ptr(), stream)
+        if rc != 0:
+            L.check(self._lib, rc)
+        self._aug_draw += 1
         return o
 
     def sample(self, batch_size):
@@ -501,7 +547,8 @@ class ReplayMemory:
         self.stream_t             # (fetches the device-resident counters after device rounds; refreshes self.t)
         meta = dict(version=1, capacity=self.capacity, history=self.history, n=self.n, discount=self.discount,
                     priority_weight=self.priority_weight, priority_exponent=self.priority_exponent, t=self.t,
-                    streams=self.streams, stream_t=[int(x) for x in self.stream_t], seed=self._seed, columns={k: spec[k][1] for k in self._COLUMNS}, header=bytes(hdr).hex())
+                    streams=self.streams, stream_t=[int(x) for x in self.stream_t], seed=self._seed,
+                    augment_pad=int(self.augment_pad), aug_draw=int(self._aug_draw), columns={k: spec[k][1] for k in self._COLUMNS}, header=bytes(hdr).hex())
         blob = json.dumps(meta).encode()
         fileobj.write(b"RBRPLY01" + struct.pack("<q", len(blob)) + blob)
         stage = np.empty(chunk_bytes, dtype=np.uint8)
@@ -525,8 +572,10 @@ class ReplayMemory:
         meta = json.loads(fileobj.read(n).decode())
         args = types.SimpleNamespace(device=device, history_length=meta["history"], discount=meta["discount"],
                                      multi_step=meta["n"], priority_weight=meta["priority_weight"],
-                                     priority_exponent=meta["priority_exponent"])
+                                     priority_exponent=meta["priority_exponent"],
+                                     augment_pad=meta.get("augment_pad", 0))                  # (older streams: no augmentation)
         mem = cls(args, meta["capacity"], seed=meta["seed"], streams=meta.get("streams", 1))   # (older streams: one stream)
+        mem._aug_draw = int(meta.get("aug_draw", 0))
         mem.t = meta["t"]
         mem.stream_t = np.array(meta.get("stream_t", [meta["t"]]), dtype=np.int32)
         b, spec = mem._column_spec()
@@ -582,7 +631,7 @@ class ReplayMemory:
         stream_t = self.stream_t  # (fetches the device-resident counters after device rounds)
         st = {k: v for k, v in self.__dict__.items()
               if k not in ("_stream_t_dev", "_stream_t_host", "_dev_round", "_lib", "_h", "_handle", "_pending", "_applied", "_stage", "transitions", "_out", "_uu", "_upd", "_neg_beta_dev",
-                           "_neg_beta_val", "_bufs", "_idx_keep")}
+                           "_neg_beta_val", "_bufs", "_idx_keep", "_shifts_in")}
         st["device"] = str(self.device)
         st["stream_t"] = stream_t
         st["_dump"] = dump
@@ -592,6 +641,8 @@ class ReplayMemory:
         dump = st.pop("_dump")
         stream_t = st.pop("stream_t", None)
         self.__dict__.update(st)
+        self.augment_pad = self._checked_pad(st.get("augment_pad", 0))      # (a pickle from before the option: off, draw 0)
+        self._aug_draw = int(st.get("_aug_draw", 0))
         self.device = torch.device(self.device)
         self._lib = L.load()
         # (a pickle from before interleaved streams: one stream)
