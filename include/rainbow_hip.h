@@ -660,7 +660,7 @@ int rb_learner_train_step(rb_learner_t* l, const rb_train_step_t* a, rb_stream_t
  *   the other way round (the priorities were written back in call k's backward), so 30 us of pure HBM streaming run
  *   beside the sampler's one latency-bound workgroup instead of in front of it.  Same arithmetic in the same order: the
  *   parameters are bit-identical to the undeferred ones.  EVERY other learner entry point that touches parameters,
- *   moments, gradients or the norm (act, act_batch, learn*, clip_*, sync_target, finish_grads, debug_read) first runs the
+ *   moments, gradients or the norm (act, act_batch, learn*, clip_*, sync_target, set_target_tau, target_ema, finish_grads, debug_read) first runs the
  *   pending pass as a launch of its own, on the stream it is given — use ONE stream per handle.  A caller that reads the
  *   borrowed buffers itself (params_dev, exp_avg, exp_avg_sq, grads_dev, norm_dev) calls rb_learner_flush first.       */
 #define RB_LEARNER_FUSE_FC_H_DW 1
@@ -762,6 +762,23 @@ int rb_learner_set_rng(rb_learner_t* l, uint64_t seed, uint64_t epoch, rb_stream
 
 /* Agent.update_target_net (agent.py:102-103): params AND noise, device-to-device.   */
 int rb_learner_sync_target(rb_learner_t* l, rb_stream_t stream);
+
+/* A target network that follows EVERY optimiser step (DrQ / SPR: tau = 1; SR-SPR / BBF: tau = 0.005) instead of being copied
+ * every few thousand: target <- target + tau * (online - target), element for element on the PARAMETERS (the target's noise is
+ * redrawn before every use and is left alone; rb_learner_sync_target keeps working and keeps copying both).
+ * rb_learner_set_target_tau: tau in [0, 1] (anything else: RB_ERR_INVALID).  A pending optimiser pass runs first, with the tau
+ *   it was issued under.  From then on every optimiser pass the library issues (rb_learner_clip_adam, _deferred,
+ *   rb_learner_train_step[_dist]) moves the target INSIDE the pass, right behind the parameter update, where the new value is
+ *   still in a register: no launch of its own, the pass stays hosted by the next sampler launch (RB_LEARNER_DEFER_UPDATE), and
+ *   the only extra traffic is the target array itself — read and written for tau < 1, only written for tau = 1 (the target
+ *   then equals the online parameters bit for bit).  Under RB_LEARNER_FUSE_FC_H_DW the EMA is one small launch behind the
+ *   pass instead.  A step the pass skips (failed draw) does not move the target either.  tau = 0 (the default) switches it off:
+ *   every launch is then exactly what it is without this call.  With a pass pending the target is one step behind, like the
+ *   parameters: rb_learner_flush before reading target_params_dev.
+ * rb_learner_target_ema: ONE such step now, unconditionally, as a launch of its own (a pending pass runs first): for a caller
+ *   whose optimiser is not the library's (call it right after that optimiser's step).  tau = 0 does nothing.              */
+int rb_learner_set_target_tau(rb_learner_t* l, float tau, rb_stream_t stream);
+int rb_learner_target_ema(rb_learner_t* l, float tau, rb_stream_t stream);
 
 /* White-box access for parity tests: copies an internal activation to out_dev.
  * what: 0 log_ps_a [B][atoms], 1 m (projected target) [B][atoms], 2 argmax a* i32[B],

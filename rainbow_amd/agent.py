@@ -176,7 +176,7 @@ class Agent:
         self._noise_layout = _query_layout(self._lib, self._cfg, self._lib.rb_learner_noise_layout)
         d = self.device
         self._params = torch.zeros(n_params.value, dtype=torch.float32, device=d)          # online, flat
-        self.target_params = torch.zeros(n_params.value, dtype=torch.float32, device=d)
+        self._target_params = torch.zeros(n_params.value, dtype=torch.float32, device=d)
         self._grads = torch.zeros(n_params.value, dtype=torch.float32, device=d)
         self.noise = torch.zeros(n_noise.value, dtype=torch.float32, device=d)
         self.target_noise = torch.zeros(n_noise.value, dtype=torch.float32, device=d)
@@ -184,7 +184,7 @@ class Agent:
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
         with torch.cuda.device(d):
             L.check(self._lib, self._lib.rb_learner_create(
-                C.byref(self._h), C.byref(self._cfg), self._params.data_ptr(), self.target_params.data_ptr(),
+                C.byref(self._h), C.byref(self._cfg), self._params.data_ptr(), self._target_params.data_ptr(),
                 self._grads.data_ptr(), self.noise.data_ptr(), self.target_noise.data_ptr(), seed))
 
         self._init_parameters(float(getattr(args, "noisy_std", 0.1)))
@@ -270,6 +270,13 @@ class Agent:
         L.check(self._lib, self._lib.rb_learner_set_flags(
             self._h, (L.LEARNER_FUSE_FC_H_DW if self._fused_dw else 0) | (L.LEARNER_DEFER_UPDATE if self._defer_update else 0)
             | (L.LEARNER_IMPLICIT_SIGMA if self._implicit_sigma else 0)))
+        # args.target_tau > 0: the target network follows EVERY optimiser step, target += tau * (online - target), inside the
+        # clip + Adam pass (include/rainbow_hip.h rb_learner_set_target_tau; tau = 1: DrQ / SPR, 0.005: SR-SPR / BBF) — the
+        # loops of rainbow_amd.loop then skip the periodic hard sync.  0 (the default): nothing changes.
+        self._target_tau = 0.0
+        tau = float(getattr(args, "target_tau", 0.0) or 0.0)
+        if tau != 0.0:
+            self.target_tau = tau
 
     # The flat tensors the library borrows.  With a deferred optimiser pass pending they are one update behind: reading them
     # through these names runs the pass first.
@@ -287,6 +294,36 @@ class Agent:
     def _norm(self):
         self.flush()
         return self._norm_buf
+
+    @property
+    def target_params(self):
+        """The target network's flat parameters.  With an EMA target (target_tau > 0) a pending optimiser pass moves them too:
+        it runs first, as for `params`; otherwise the tensor is handed out as it always was."""
+        if self._target_tau > 0:
+            self.flush()
+        return self._target_params
+
+    @property
+    def target_tau(self):
+        return self._target_tau
+
+    @target_tau.setter
+    def target_tau(self, tau):
+        tau = float(tau)
+        if not 0.0 <= tau <= 1.0:                         # (also NaN)
+            raise ValueError("target_tau must be in [0, 1], got %r" % tau)
+        if tau == self._target_tau:
+            return
+        # (the library runs a pending pass first: its device-side arguments carry the old tau)
+        L.check(self._lib, self._lib.rb_learner_set_target_tau(self._h, tau, self._stream()))
+        self._update_pending = False
+        self._target_tau = tau
+
+    def target_ema(self, tau):
+        """One EMA step of the target towards the online parameters now (rb_learner_target_ema): what learn() does itself, after
+        its own optimiser step, when the optimiser is not the library's (RAINBOW_AMD_FUSED_ADAM=0)."""
+        L.check(self._lib, self._lib.rb_learner_target_ema(self._h, float(tau), self._stream()))
+        self._update_pending = False
 
     def flush(self):
         """Run the optimiser pass the last learn() left pending (RAINBOW_AMD_DEFER_UPDATE), if any."""
@@ -697,6 +734,8 @@ class Agent:
             L.check(self._lib, self._lib.rb_learner_clip_grad(self._h, float(self.norm_clip), self._norm_buf.data_ptr(),
                                                               stream))                    # agent.py:97
             self.optimiser.step()                                                          # agent.py:98
+            if self._target_tau > 0:             # (torch's own Adam: the library's passes never run, the EMA is a launch of its own)
+                L.check(self._lib, self._lib.rb_learner_target_ema(self._h, self._target_tau, stream))
         if device_mem:
             if not fused_update:
                 mem.update_priorities(idxs, self._loss, _immediate=True)                   # agent.py:100, no D2H
@@ -825,7 +864,8 @@ class Agent:
 
     # ------------------------------------------------------------------ exact resume
     def checkpoint(self, path=None):
-        """Everything the learner needs to continue bit-for-bit: online / target parameters, both noise buffers, Adam
+        """Everything the learner needs to continue bit-for-bit: online / target parameters (a pending optimiser pass, which
+        with target_tau > 0 moves the target too, has run before they are copied), target_tau, both noise buffers, Adam
         moments + step, the Philox (seed, epoch) of the noise generator and the pending-resample flag.  The reference's
         save() (weights only, agent.py:106-107) stays what main.py:182 calls; this is the superset a resumable run needs
         (main.py has no such thing: it restarts the optimiser).  Returns the dict; writes it with torch.save if `path`."""
@@ -836,10 +876,11 @@ class Agent:
         seed, epoch = C.c_uint64(0), C.c_uint64(0)
         L.check(self._lib, self._lib.rb_learner_get_rng(self._h, C.byref(seed), C.byref(epoch), self._stream()))
         st = self.optimiser.state[self._params]
-        ck = dict(version=1, config=bytes(self._cfg), params=self._params.detach().cpu(), target_params=self.target_params.cpu(),
+        ck = dict(version=1, config=bytes(self._cfg), params=self._params.detach().cpu(), target_params=self._target_params.cpu(),
                   noise=self.noise.cpu(), target_noise=self.target_noise.cpu(), exp_avg=st["exp_avg"].cpu(),
                   exp_avg_sq=st["exp_avg_sq"].cpu(), adam_step=float(st["step"]), rng_seed=int(seed.value),
-                  rng_epoch=int(epoch.value), noise_pending=bool(self._noise_pending), training=bool(self.training))
+                  rng_epoch=int(epoch.value), noise_pending=bool(self._noise_pending), training=bool(self.training),
+                  target_tau=float(self._target_tau))
         if path is not None:
             torch.save(ck, path)
         return ck
@@ -855,7 +896,7 @@ class Agent:
             raise RuntimeError("checkpoint does not match this Agent's configuration")
         with torch.no_grad():
             self._params.copy_(ck["params"])
-            self.target_params.copy_(ck["target_params"])
+            self._target_params.copy_(ck["target_params"])
             self.noise.copy_(ck["noise"])
             self.target_noise.copy_(ck["target_noise"])
             st = self.optimiser.state[self._params]
@@ -868,6 +909,8 @@ class Agent:
         self._noise_pending = bool(ck["noise_pending"])
         self.training = bool(ck["training"])
         self._noise_jobs = {}
+        if "target_tau" in ck:                      # (checkpoints from before the EMA target carry none: the agent keeps its own)
+            self.target_tau = ck["target_tau"]
 
     def save(self, path, name="model.pth"):
         torch.save(self.state_dict(), os.path.join(path, name))

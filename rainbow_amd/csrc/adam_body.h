@@ -43,12 +43,18 @@ struct ClipAdamArgs {
                                // below hole_lo4 and quad j + hole4 from there on (hole4 = 0: no pairing)
   int pair_blk0;               // first pair workgroup (= number of plain workgroups)
   int pair_f4, pair_split_row; // quads per weight row; rows >= split_row take eps_in from the second stream's vector
+  float tau;                   // (in what was padding) target EMA, see `t` below: 0 = off, 1 = the target copies p
   const float* pair_eout;      // [rows]
   const float* pair_ein;       // [2][4 * pair_f4]
   int32_t* pair_clipped;       // written by the pair pass: 1 = the clip bit and the SCALED gradients (sigma's included) were stored
                                // back, exactly as the reference leaves .grad — a later materialisation must not redo them from
                                // the scaled g_mu (the product would round in another order); 0 = nothing was stored
+  // TARGET EMA (rb_learner_set_target_tau; the EMA instantiations of the kernels only): non-NULL = the target network's flat
+  // parameters follow the update in the same pass, t += tau (p_new - t) element for element (rb_ema_elem) — the new p is in a
+  // register here, a pass of its own would read it back.  A skipped update (batch_status) leaves t alone as it leaves p.
+  float* t;
 };
+static_assert(sizeof(ClipAdamArgs) <= 256, "ClipAdamArgs: the device copy (adam_args_dev, rb_debug_adam_pass) is 256 bytes");
 // (IEEE sqrt and divisions, as torch computes them: hardware rcp / approximate sqrt measured 1.5 us faster per launch
 // and stay far inside the test tolerance, but the update would no longer be the reference's formula rounding for rounding)
 __device__ __forceinline__ void rb_adam_elem(float& p, float& g, float& m, float& v, float coef, const ClipAdamArgs& a) {
@@ -63,6 +69,18 @@ __device__ __forceinline__ void rb_adam_quad(float4& P, float4& G, float4& M, fl
   rb_adam_elem(P.y, G.y, M.y, V.y, coef, a);
   rb_adam_elem(P.z, G.z, M.z, V.z, coef, a);
   rb_adam_elem(P.w, G.w, M.w, V.w, coef, a);
+}
+
+// The target network's EMA step on the freshly written parameter: t <- t + tau (p - t), one rounding for the difference and one
+// for the fma (written out like m's: the unit is built with -ffp-contract=off).  tau == 1 is a case of its own for the
+// callers (rb_ema_quad: t = p, and t is never loaded): fmaf(1, p - t, t) is not p bit for bit.
+__device__ __forceinline__ void rb_ema_elem(float& t, float p, float tau) {
+  t = fmaf(tau, p - t, t);
+}
+// copy = (tau == 1), wave-uniform
+__device__ __forceinline__ void rb_ema_quad(float4& T, const float4& P, float tau, bool copy) {
+  if (copy) { T = P; return; }
+  rb_ema_elem(T.x, P.x, tau); rb_ema_elem(T.y, P.y, tau); rb_ema_elem(T.z, P.z, tau); rb_ema_elem(T.w, P.w, tau);
 }
 
 // The plain pass (no skipped range) as hosted workgroups: block `eb` of `nblk`.  The element loops work for any block size that
@@ -152,6 +170,9 @@ __device__ __forceinline__ bool rb_adam_hosted_prologue(ClipAdamArgs& a, int eb,
 // the prologue's requests and the noise factors eps_out / eps_in of the thread's pairs (10 registers; their products are formed
 // when the update needs them.  With one pair per thread the pass streamed too thinly to gain anything: 38.8 against 36.3 us
 // for the hosting launch).
+// EMA: the target's (mu, sigma) quads join the same trip (requested last: consumed last; not at all when tau == 1) and are
+// written with the same write-through stores.
+template <bool EMA>
 __device__ __forceinline__ void rb_adam_hosted_pairs(ClipAdamArgs& a, int eb, int pb, float* s_red16) {
   constexpr int PU = 2;
   const unsigned T = blockDim.x;
@@ -181,6 +202,17 @@ __device__ __forceinline__ void rb_adam_hosted_pairs(ClipAdamArgs& a, int eb, in
     M[u] = rb_ld4_buf(bm, 16 * i, 0); V[u] = rb_ld4_buf(bv, 16 * i, 0);
     P2[u] = rb_ld4_buf(bp, 16 * i2, 0); M2[u] = rb_ld4_buf(bm, 16 * i2, 0); V2[u] = rb_ld4_buf(bv, 16 * i2, 0);
   }
+  const bool ema_copy = EMA && a.tau == 1.0f;            // uniform
+  float4 TG[EMA ? PU : 1], TG2[EMA ? PU : 1];
+  if (EMA && !ema_copy) {
+    const rb_buf bt = rb_make_buf(a.t);
+#pragma unroll
+    for (int u = 0; u < PU; ++u) {
+      unsigned j = base + u * T;
+      if (j >= len4) j = len4 - 1;
+      TG[u] = rb_ld4_buf(bt, 16 * (mu4 + j), 0); TG2[u] = rb_ld4_buf(bt, 16 * (mu4 + j + len4), 0);
+    }
+  }
   float coef;
   if (!rb_adam_hosted_prologue(a, eb, q, s_red16, &coef)) return;
   if (pb == 0 && threadIdx.x == 0 && a.pair_clipped) rb_st1_wt(reinterpret_cast<float*>(a.pair_clipped), 0, __builtin_bit_cast(float, coef < 1.0f ? 1 : 0));
@@ -198,15 +230,19 @@ __device__ __forceinline__ void rb_adam_hosted_pairs(ClipAdamArgs& a, int eb, in
     rb_st4_wt(a.p, 16 * i, P[u]); rb_st4_wt(a.m, 16 * i, M[u]); rb_st4_wt(a.v, 16 * i, V[u]);
     rb_st4_wt(a.p, 16 * i2, P2[u]); rb_st4_wt(a.m, 16 * i2, M2[u]); rb_st4_wt(a.v, 16 * i2, V2[u]);
     if (coef < 1.0f) { rb_st4_wt(a.g, 16 * i, G[u]); rb_st4_wt(a.g, 16 * i2, G2); }
+    if (EMA) {
+      rb_ema_quad(TG[u], P[u], a.tau, ema_copy); rb_ema_quad(TG2[u], P2[u], a.tau, ema_copy);
+      rb_st4_wt(a.t, 16 * i, TG[u]); rb_st4_wt(a.t, 16 * i2, TG2[u]);
+    }
   }
 }
 
-template <int UNROLL>
+template <int UNROLL, bool EMA = false>
 __device__ __forceinline__ void rb_adam_hosted_block(const ClipAdamArgs* ad, int eb, int nblk, float* s_red16 /* [18] */) {
   ClipAdamArgs a = rb_ld_uniform(ad);                    // SGPRs; each role keeps only the fields it uses
   const int nplain = a.hole4 > 0 ? a.pair_blk0 : nblk;
   if (eb >= nplain) {                                    // block-uniform: a (mu, sigma) pair workgroup
-    rb_adam_hosted_pairs(a, eb, eb - nplain, s_red16);
+    rb_adam_hosted_pairs<EMA>(a, eb, eb - nplain, s_red16);
     return;
   }
   const unsigned T = blockDim.x;
@@ -227,6 +263,22 @@ __device__ __forceinline__ void rb_adam_hosted_block(const ClipAdamArgs* ad, int
     P[u] = rb_ld4_buf(bp, 16 * i, 0); G[u] = rb_ld4_buf(bg, 16 * i, 0);
     M[u] = rb_ld4_buf(bm, 16 * i, 0); V[u] = rb_ld4_buf(bv, 16 * i, 0);
   }
+  // EMA: the target's quads (and its tail element) behind them in the same trip — consumed last; none when tau == 1
+  const bool ema_copy = EMA && a.tau == 1.0f;            // uniform
+  const bool has_tail = eb == nplain - 1 && ((a.n >> 2) << 2) + threadIdx.x < a.n;
+  const unsigned tail_off = (unsigned)(4 * (((a.n >> 2) << 2) + threadIdx.x));
+  float4 TG[EMA ? UNROLL : 1];
+  float tg_tail = 0.0f;
+  if (EMA && !ema_copy) {
+    const rb_buf bt = rb_make_buf(a.t);
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      unsigned j = base + u * T;
+      if (j >= nv4) j = nv4 > 0 ? nv4 - 1 : 0;
+      TG[u] = rb_ld4_buf(bt, 16 * real_of(j), 0);
+    }
+    if (has_tail) tg_tail = rb_ld1_buf(bt, tail_off, 0);
+  }
   float coef;
   if (!rb_adam_hosted_prologue(a, eb, q, s_red16, &coef)) return;
 #pragma unroll
@@ -237,6 +289,10 @@ __device__ __forceinline__ void rb_adam_hosted_block(const ClipAdamArgs* ad, int
     rb_adam_quad(P[u], G[u], M[u], V[u], coef, a);
     rb_st4_wt(a.p, 16 * i, P[u]); rb_st4_wt(a.m, 16 * i, M[u]); rb_st4_wt(a.v, 16 * i, V[u]);
     if (coef < 1.0f) rb_st4_wt(a.g, 16 * i, G[u]);
+    if (EMA) {
+      rb_ema_quad(TG[u], P[u], a.tau, ema_copy);
+      rb_st4_wt(a.t, 16 * i, TG[u]);
+    }
   }
   // tail (n % 4 elements): the last plain block's first threads
   if (eb == nplain - 1) {
@@ -247,10 +303,15 @@ __device__ __forceinline__ void rb_adam_hosted_block(const ClipAdamArgs* ad, int
       rb_adam_elem(p, g, m, v, coef, a);
       rb_st1_wt(a.p, o, p); rb_st1_wt(a.m, o, m); rb_st1_wt(a.v, o, v);
       if (coef < 1.0f) rb_st1_wt(a.g, o, g);
+      if (EMA) {
+        if (ema_copy) tg_tail = p; else rb_ema_elem(tg_tail, p, a.tau);
+        rb_st1_wt(a.t, o, tg_tail);
+      }
     }
   }
 }
 
 // The pending pass as a launch of its own through the HOSTED body (adam_kernels.h k_adam_pending, in the learner's unit; arguments
 // in device memory): what runs a pass with (mu, sigma) pairing outside a sampler launch.  Returns RB_OK or RB_ERR_HIP.
-int rb_launch_adam_pending(const ClipAdamArgs* args_dev, int blocks, void* stream);
+// ema: the pass's arguments carry a target (k_adam_pending_ema; the caller knows: the arguments live on the device).
+int rb_launch_adam_pending(const ClipAdamArgs* args_dev, int blocks, void* stream, bool ema = false);

@@ -97,8 +97,12 @@ __device__ __forceinline__ void rb_fused_dw_adam_tile(const ClipAdamArgs& a, con
   }
 }
 #define RB_ADAM_MINWAVES 1
-template <int RB_ADAM_UNROLL, bool WT, bool FUSED>   // float4 quadruples (p, g, m, v) in flight per thread; WT: write-through stores
+// EMA (never with FUSED: the tile pass's register budget shaped its design; k_target_ema follows that launch instead): the
+// target's quads are loaded with the others and written behind them (adam_body.h rb_ema_elem).  An instantiation of its own,
+// chosen by the host: with a.t == NULL the plain one runs, the kernel it has always been.
+template <int RB_ADAM_UNROLL, bool WT, bool FUSED, bool EMA = false>   // float4 quadruples (p, g, m, v) in flight per thread; WT: write-through stores
 __global__ __launch_bounds__(256, RB_ADAM_MINWAVES) void k_clip_adam(ClipAdamArgs a, FusedDwAdamArgs f) {
+  static_assert(!(EMA && FUSED), "k_clip_adam: the fused tile pass has no in-pass EMA");
   __shared__ float s_red[18];      // [0, 16) rb_block_sum's wave slots; [16], [17] the bias-correction scalars (slots of their own:
                                    // thread 0 writes them while other waves may still be reading the wave slots of the sum —
                                    // the host interpreter's schedule turned that into a wrong clip coefficient for every thread
@@ -118,6 +122,12 @@ __global__ __launch_bounds__(256, RB_ADAM_MINWAVES) void k_clip_adam(ClipAdamArg
       idx[u] = i;
       P[u] = rb_ld4(a.p + 4 * i); G[u] = rb_ld4(a.g + 4 * i); M[u] = rb_ld4(a.m + 4 * i); V[u] = rb_ld4(a.v + 4 * i);
     }
+  }
+  const bool ema_copy = EMA && a.tau == 1.0f;                       // uniform
+  float4 TG[EMA ? RB_ADAM_UNROLL : 1];
+  if (EMA && !ema_copy) {
+#pragma unroll
+    for (int u = 0; u < RB_ADAM_UNROLL; ++u) TG[u] = rb_ld4(a.t + 4 * idx[u]);
   }
   if (a.batch_status && *a.batch_status != 0) {                     // block-uniform (every block reads the same word)
     if (blockIdx.x == 0 && threadIdx.x == 0 && a.norm_out) *a.norm_out = 0.0f;
@@ -157,6 +167,11 @@ __global__ __launch_bounds__(256, RB_ADAM_MINWAVES) void k_clip_adam(ClipAdamArg
       rb_st4(a.p + 4 * i, P[u]); rb_st4(a.m + 4 * i, M[u]); rb_st4(a.v + 4 * i, V[u]);
     }
     if (coef < 1.0f) rb_st4(a.g + 4 * i, G[u]);
+    if (EMA) {
+      rb_ema_quad(TG[u], P[u], a.tau, ema_copy);
+      if (WT) rb_st4_wt(a.t, (unsigned)(16 * i), TG[u]);
+      else rb_st4(a.t + 4 * i, TG[u]);
+    }
   }
   // tail (n % 4 elements): last block's first threads
   if (blockIdx.x == gridDim.x - 1) {
@@ -166,6 +181,11 @@ __global__ __launch_bounds__(256, RB_ADAM_MINWAVES) void k_clip_adam(ClipAdamArg
       rb_adam_elem(p, g, m, v, coef, a);
       a.p[t] = p; a.m[t] = m; a.v[t] = v;
       if (coef < 1.0f) a.g[t] = g;
+      if (EMA) {
+        float tg = p;
+        if (!ema_copy) { tg = a.t[t]; rb_ema_elem(tg, p, a.tau); }
+        a.t[t] = tg;
+      }
     }
   }
 }
@@ -199,11 +219,51 @@ __global__ __launch_bounds__(256) void k_adam_pending(const ClipAdamArgs* ad) {
   rb_adam_hosted_block<4>(ad, (int)blockIdx.x, (int)gridDim.x, s_adam);
 }
 
+// the same with the target EMA (arguments with a target pointer: rb_launch_adam_pending is told)
+__global__ __launch_bounds__(256) void k_adam_pending_ema(const ClipAdamArgs* ad) {
+  __shared__ float s_adam[18];
+  rb_adam_hosted_block<4, true>(ad, (int)blockIdx.x, (int)gridDim.x, s_adam);
+}
+
+// The EMA as a launch of its own: t <- t + tau (p - t) over n floats (t = p for tau == 1), skipped like the optimiser pass when
+// the batch status says the draw failed (status may be NULL).  Behind the fused tile pass (k_clip_adam<4, true, true>, which
+// carries no EMA), and rb_learner_target_ema.  Grid-stride over quads, the n % 4 tail by block 0's first threads.
+__global__ __launch_bounds__(256) void k_target_ema(float* t, const float* p, int64_t n, float tau, const int32_t* status) {
+  if (status && *status != 0) return;                               // block-uniform
+  const bool copy = tau == 1.0f;
+  const int64_t n4 = n >> 2;
+  for (int64_t i0 = (int64_t)blockIdx.x * 1024 + threadIdx.x; i0 < n4; i0 += (int64_t)gridDim.x * 1024) {
+    float4 P[4], T[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t i = i0 + u * 256 < n4 ? i0 + u * 256 : n4 - 1;  // clamped load, masked store
+      P[u] = rb_ld4(p + 4 * i);
+      if (!copy) T[u] = rb_ld4(t + 4 * i);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t i = i0 + u * 256;
+      if (i >= n4) continue;
+      rb_ema_quad(T[u], P[u], tau, copy);
+      rb_st4(t + 4 * i, T[u]);
+    }
+  }
+  if (blockIdx.x == 0) {
+    const int64_t e = (n4 << 2) + threadIdx.x;
+    if (e < n) {
+      float tg = p[e];
+      if (!copy) { tg = t[e]; rb_ema_elem(tg, p[e], tau); }
+      t[e] = tg;
+    }
+  }
+}
+
 }  // extern "C"
 
 // (declared in adam_body.h: replay.hip calls it across translation units)
-int rb_launch_adam_pending(const ClipAdamArgs* args_dev, int blocks, void* stream) {
-  RB_LAUNCH_T("clip_adam:k_adam_pending", k_adam_pending, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, args_dev);
+int rb_launch_adam_pending(const ClipAdamArgs* args_dev, int blocks, void* stream, bool ema) {
+  if (ema) RB_LAUNCH_T("clip_adam:k_adam_pending", k_adam_pending_ema, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, args_dev);
+  else RB_LAUNCH_T("clip_adam:k_adam_pending", k_adam_pending, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, args_dev);
   RB_LAUNCH_CHECK();
   return RB_OK;
 }

@@ -104,7 +104,7 @@ static NoiseJob make_noise_job(rb_learner* l, int which) {
   j.seed = l->seed; j.ctr = l->noise_ctr;
   j.nblk = (int)rb_div_up(j.map.seg_begin[8], 256); j.nets = which == 2 ? 2 : 1;
   j.dev = l->job_dev + which;
-  j.adam_dev = nullptr; j.adam_blocks = 0;
+  j.adam_dev = nullptr; j.adam_blocks = 0; j.adam_ema = 0;
   return j;
 }
 // device copies of the three job variants (a hosting kernel reads them through NoiseJob::dev): at creation and whenever the

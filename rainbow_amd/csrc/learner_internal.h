@@ -240,6 +240,7 @@ struct rb_learner {
   ClipAdamArgs* adam_args_dev;   // the pending pass's arguments in device memory (rewritten only when they change)
   ClipAdamArgs adam_args_host;   // ... and what that memory holds
   int adam_args_valid, adam_pending, adam_blocks;
+  float target_tau;              // rb_learner_set_target_tau: > 0 = every optimiser pass moves p_target by this EMA (0: off)
   // The early draw (RB_OPTS spec_draw=1, OFF by default; replay_internal.h rb_replay_spec_launch): from the second back-to-back
   // rb_learner_train_step on the same replay with nothing in between, the priority write-back leaves the hidden layer's backward
   // launch and runs — together with the NEXT call's draw — on the replay's own stream as soon as the head kernel is done; the next

@@ -66,4 +66,5 @@ struct NoiseJob {
   // ClipAdamArgs and the number of 256-thread workgroups it needs (0 = none).  Filled in by rb_learner_train_step only.
   const void* adam_dev;
   int adam_blocks;
+  int adam_ema;           // those arguments carry a target pointer (rb_learner_set_target_tau): the hosting launch picks its EMA instantiation
 };

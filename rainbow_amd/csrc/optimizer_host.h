@@ -25,12 +25,13 @@ static int flush_update(rb_learner* l, hipStream_t stream) {
   ClipAdamArgs a = l->adam_args_host;
   int blocks = l->adam_blocks;
   if (a.pair_len4 > 0) {        // the pending pass forms the sigma gradient itself: the hosted body as a launch of its own
-    const int rc = rb_launch_adam_pending(l->adam_args_dev, blocks, stream);      // (its arguments are in device memory already)
+    const int rc = rb_launch_adam_pending(l->adam_args_dev, blocks, stream, a.t != nullptr);      // (its arguments are in device memory already)
     if (rc != RB_OK) return rc;
     l->adam_pending = 0;
     return RB_OK;
   }
-  RB_LAUNCH_T("clip_adam:k_clip_adam", (k_clip_adam<4, true, false>), dim3((unsigned)blocks), dim3(256), stream, a, f);
+  if (a.t) RB_LAUNCH_T("clip_adam:k_clip_adam", (k_clip_adam<4, true, false, true>), dim3((unsigned)blocks), dim3(256), stream, a, f);
+  else RB_LAUNCH_T("clip_adam:k_clip_adam", (k_clip_adam<4, true, false>), dim3((unsigned)blocks), dim3(256), stream, a, f);
   RB_LAUNCH_CHECK();
   l->adam_pending = 0;
   return RB_OK;
@@ -53,7 +54,19 @@ static bool attach_pending_pass(rb_learner* l, const rb_noise_job_t* job_in, int
   if (!l->adam_pending || batch > 256) return false;
   NoiseJob* nj = reinterpret_cast<NoiseJob*>(job_out);
   nj->adam_dev = l->adam_args_dev; nj->adam_blocks = l->adam_blocks;
+  nj->adam_ema = l->adam_args_host.t != nullptr ? 1 : 0;
   return true;
+}
+
+// One EMA step of the target towards the online parameters as a launch of its own (adam_kernels.h k_target_ema): behind the fused
+// tile pass, and rb_learner_target_ema (status = NULL: unconditional).
+static int launch_target_ema(rb_learner* l, float tau, const int32_t* status, hipStream_t stream) {
+  const int64_t n = l->L.n_params;
+  const int64_t n4 = n >> 2;
+  RB_LAUNCH_T("clip_adam:k_target_ema", k_target_ema, dim3((unsigned)rb_div_up(n4 > 0 ? n4 : 1, 256 * 4)), dim3(256), stream, l->p_target,
+              (const float*)l->p_online, n, tau, status);
+  RB_LAUNCH_CHECK();
+  return RB_OK;
 }
 
 static int clip_adam_impl(rb_learner* l, float max_norm, float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2,
@@ -80,6 +93,8 @@ static int clip_adam_impl(rb_learner* l, float max_norm, float* exp_avg, float* 
   a.neg_step_size = (float)(-(lr / bc1)); a.bc2_sqrt = (float)sqrt(bc2); a.eps = (float)eps;
   a.step_dev = step == 0 ? l->step_ctr : nullptr; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2;
   a.batch_status = l->status_copy;        // (k_head's copy of l->batch_status: see status_copy)
+  const bool ema = l->target_tau > 0.0f;  // (both fields stay zero otherwise: the argument block, and with it every launch, is today's)
+  if (ema && !l->dw_deferred) { a.t = l->p_target; a.tau = l->target_tau; }
   const int64_t n4 = n >> 2;
   // 4 quadruples per thread: measured best of {2, 4, 8} on MI355X (254.3 / 255.6 / 256.6 us per step)
   // write-through stores (same-box A/B 253.7 -> 250.8 us per step) through buffer instructions: offsets are 31-bit
@@ -99,6 +114,10 @@ static int clip_adam_impl(rb_learner* l, float max_norm, float* exp_avg, float* 
     const unsigned grid = (unsigned)(f.n_tile_blocks + rb_div_up(n4 - a.skip_len4 > 0 ? n4 - a.skip_len4 : 1, 256 * 4));
     RB_LAUNCH_T("clip_adam:k_clip_adam", (k_clip_adam<4, true, true>), dim3(grid), dim3(256), stream, a, f);
     l->dw_deferred = 0;
+    if (ema) {      // the tile pass carries no EMA (adam_kernels.h): the stand-alone launch right behind it, same rule, same skip
+      RB_LAUNCH_CHECK();
+      return launch_target_ema(l, l->target_tau, a.batch_status, stream);
+    }
   } else {
     unsigned grid = (unsigned)rb_div_up(n4 > 0 ? n4 : 1, 256 * 4);
     const bool will_defer = defer && a.step_dev != nullptr && a.nparts > 0 && l->adam_args_dev != nullptr;
@@ -129,13 +148,30 @@ static int clip_adam_impl(rb_learner* l, float max_norm, float* exp_avg, float* 
       l->adam_blocks = (int)grid;
       return RB_OK;
     }
-    RB_LAUNCH_T("clip_adam:k_clip_adam", (k_clip_adam<4, true, false>), dim3(grid), dim3(256), stream, a, f);
+    if (ema) RB_LAUNCH_T("clip_adam:k_clip_adam", (k_clip_adam<4, true, false, true>), dim3(grid), dim3(256), stream, a, f);
+    else RB_LAUNCH_T("clip_adam:k_clip_adam", (k_clip_adam<4, true, false>), dim3(grid), dim3(256), stream, a, f);
   }
   RB_LAUNCH_CHECK();
   return RB_OK;
 }
 
 extern "C" {
+
+int rb_learner_set_target_tau(rb_learner_t* l, float tau, rb_stream_t stream) {
+  RB_REQUIRE(l != nullptr, "rb_learner_set_target_tau: NULL handle");
+  RB_REQUIRE(tau >= 0.0f && tau <= 1.0f, "rb_learner_set_target_tau: tau must be in [0, 1], got %g", (double)tau);
+  RB_FLUSH_UPDATE(l, stream);          // a pending pass's device-side arguments carry the old tau: it runs with that one
+  l->target_tau = tau;                 // (the next pass's argument block differs: the upload-on-change memcmp picks it up)
+  return RB_OK;
+}
+
+int rb_learner_target_ema(rb_learner_t* l, float tau, rb_stream_t stream) {
+  RB_REQUIRE(l != nullptr, "rb_learner_target_ema: NULL handle");
+  RB_REQUIRE(tau >= 0.0f && tau <= 1.0f, "rb_learner_target_ema: tau must be in [0, 1], got %g", (double)tau);
+  RB_FLUSH_UPDATE(l, stream);
+  if (tau == 0.0f) return RB_OK;
+  return launch_target_ema(l, tau, nullptr, (hipStream_t)stream);
+}
 
 int rb_learner_flush(rb_learner_t* l, rb_stream_t stream) {
   RB_REQUIRE(l != nullptr, "rb_learner_flush: NULL handle");
@@ -163,11 +199,11 @@ int rb_learner_pending_launched(rb_learner_t* l) {
 // the step read from `step_dev`.  `part` holds `nparts` > 0 partial sums of squares.  pair_len4 > 0 (form 1 only): quads
 // [pair_mu4, pair_mu4 + pair_len4) are a layer's mu weights, the pair_len4 quads behind them its sigma weights, whose gradient
 // the pass forms from pair_eout [rows] and pair_ein [2][4 * pair_f4] (ClipAdamArgs, adam_body.h).
-int rb_debug_adam_pass(int32_t form, float* p, float* g, float* m, float* v, int64_t n, const float* part, int32_t nparts,
-                       float max_norm, float* norm_out, const long long* step_dev, int64_t step, double lr, double beta1,
-                       double beta2, double eps, const int32_t* batch_status, int64_t pair_mu4, int64_t pair_len4, int32_t pair_f4,
-                       int32_t pair_split_row, const float* pair_eout, const float* pair_ein, int32_t* pair_clipped, void* args_dev,
-                       rb_stream_t stream_) {
+static int debug_adam_pass_impl(int32_t form, float* p, float* g, float* m, float* v, int64_t n, const float* part, int32_t nparts,
+                               float max_norm, float* norm_out, const long long* step_dev, int64_t step, double lr, double beta1,
+                               double beta2, double eps, const int32_t* batch_status, int64_t pair_mu4, int64_t pair_len4, int32_t pair_f4,
+                               int32_t pair_split_row, const float* pair_eout, const float* pair_ein, int32_t* pair_clipped, void* args_dev,
+                               float* target, float tau, rb_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   RB_REQUIRE(p && g && m && v && part && n >= 0 && n * 4 < (int64_t)0x7fffffff && nparts > 0, "rb_debug_adam_pass: bad buffers");
   RB_REQUIRE(form == 0 ? (step >= 1 && pair_len4 == 0) : (form == 1 && step_dev && args_dev), "rb_debug_adam_pass: bad form");
@@ -181,12 +217,14 @@ int rb_debug_adam_pass(int32_t form, float* p, float* g, float* m, float* v, int
   a.neg_step_size = (float)(-(lr / bc1)); a.bc2_sqrt = (float)sqrt(bc2); a.eps = (float)eps;
   a.step_dev = form == 1 ? step_dev : nullptr; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2;
   a.batch_status = batch_status;
+  a.t = target; a.tau = target ? tau : 0.0f;
   const int64_t n4 = n >> 2;
   unsigned grid = (unsigned)rb_div_up(n4 > 0 ? n4 : 1, 256 * 4);
   if (form == 0) {
     FusedDwAdamArgs f;
     memset(&f, 0, sizeof(f));
-    RB_LAUNCH((k_clip_adam<4, true, false>), dim3(grid), dim3(256), stream, a, f);
+    if (target) RB_LAUNCH((k_clip_adam<4, true, false, true>), dim3(grid), dim3(256), stream, a, f);
+    else RB_LAUNCH((k_clip_adam<4, true, false>), dim3(grid), dim3(256), stream, a, f);
     RB_LAUNCH_CHECK();
     return RB_OK;
   }
@@ -201,7 +239,27 @@ int rb_debug_adam_pass(int32_t form, float* p, float* g, float* m, float* v, int
   }
   RB_LAUNCH(k_store_adam_args, dim3(1), dim3(64), stream, a, reinterpret_cast<ClipAdamArgs*>(args_dev));
   RB_LAUNCH_CHECK();
-  return rb_launch_adam_pending(reinterpret_cast<const ClipAdamArgs*>(args_dev), (int)grid, stream);
+  return rb_launch_adam_pending(reinterpret_cast<const ClipAdamArgs*>(args_dev), (int)grid, stream, target != nullptr);
+}
+
+int rb_debug_adam_pass(int32_t form, float* p, float* g, float* m, float* v, int64_t n, const float* part, int32_t nparts,
+                       float max_norm, float* norm_out, const long long* step_dev, int64_t step, double lr, double beta1,
+                       double beta2, double eps, const int32_t* batch_status, int64_t pair_mu4, int64_t pair_len4, int32_t pair_f4,
+                       int32_t pair_split_row, const float* pair_eout, const float* pair_ein, int32_t* pair_clipped, void* args_dev,
+                       rb_stream_t stream_) {
+  return debug_adam_pass_impl(form, p, g, m, v, n, part, nparts, max_norm, norm_out, step_dev, step, lr, beta1, beta2, eps, batch_status,
+                              pair_mu4, pair_len4, pair_f4, pair_split_row, pair_eout, pair_ein, pair_clipped, args_dev, nullptr, 0.0f, stream_);
+}
+// TESTS ONLY as well: the same pass with a target attached (`target` [n], tau in (0, 1]): the EMA instantiations — form 0
+// k_clip_adam<4, true, false, true>, form 1 k_adam_pending_ema — at the lengths only rb_debug_adam_pass reaches.
+int rb_debug_adam_pass_ema(int32_t form, float* p, float* g, float* m, float* v, int64_t n, const float* part, int32_t nparts,
+                           float max_norm, float* norm_out, const long long* step_dev, int64_t step, double lr, double beta1,
+                           double beta2, double eps, const int32_t* batch_status, int64_t pair_mu4, int64_t pair_len4, int32_t pair_f4,
+                           int32_t pair_split_row, const float* pair_eout, const float* pair_ein, int32_t* pair_clipped, void* args_dev,
+                           float* target, float tau, rb_stream_t stream_) {
+  RB_REQUIRE(target != nullptr && tau > 0.0f && tau <= 1.0f, "rb_debug_adam_pass_ema: needs a target and tau in (0, 1]");
+  return debug_adam_pass_impl(form, p, g, m, v, n, part, nparts, max_norm, norm_out, step_dev, step, lr, beta1, beta2, eps, batch_status,
+                              pair_mu4, pair_len4, pair_f4, pair_split_row, pair_eout, pair_ein, pair_clipped, args_dev, target, tau, stream_);
 }
 
 // rb_learner_clip_adam that leaves the pass pending when the handle's flags say so (RB_LEARNER_DEFER_UPDATE) and it can

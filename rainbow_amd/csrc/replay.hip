@@ -516,7 +516,7 @@ static int sample_impl(rb_replay_t* r, int32_t batch, double priority_weight, co
   if (hosted) {
     blocks += (unsigned)((job.adam_blocks * 4 + RB_HOST_AU_WIDE - 1) / RB_HOST_AU_WIDE);
   } else if (adam_dev) {
-    const int rc = rb_launch_adam_pending(adam_dev, job.adam_blocks, stream);
+    const int rc = rb_launch_adam_pending(adam_dev, job.adam_blocks, stream, job.adam_ema != 0);
     if (rc != RB_OK) return rc;
     adam_dev = nullptr;
   }
@@ -531,7 +531,8 @@ static int sample_impl(rb_replay_t* r, int32_t batch, double priority_weight, co
                 job.dev, job.noise, job.noise2, job.ctr, r->fail_host, lds_top, noise_blocks, adam_dev, r->spec_res, r->spec_epoch,
                 spec_mode);
   };
-  if (wide) launch(k_sample<1024, RB_HOST_AU_WIDE>);
+  if (hosted && job.adam_ema) launch(k_sample<1024, RB_HOST_AU_WIDE, true>);    // the pass moves the target network as well
+  else if (wide) launch(k_sample<1024, RB_HOST_AU_WIDE>);
   else launch(k_sample<256, 8>);
   RB_LAUNCH_CHECK();
   return launch_gather(v, batch, win_cur, states_dev, next_states_dev, stream);

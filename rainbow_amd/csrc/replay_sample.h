@@ -214,7 +214,9 @@ __device__ __forceinline__ void rb_sample_main(const ReplayView& v, int32_t batc
   RB_STAMP_AT(5);
 }
 
-template <int MAXT, int AU>
+// EMA: the hosted pass also moves the target network (adam_body.h; arguments with a target pointer).  An instantiation of its
+// own, chosen by sample_impl from the job: the plain one stays the kernel it was, register for register.
+template <int MAXT, int AU, bool EMA = false>
 __global__ __launch_bounds__(MAXT) void k_sample(ReplayView v, int32_t batch, float neg_beta_arg,
                                                   const float* neg_beta_ptr, const double* unit_uniforms, int32_t max_attempts, uint64_t seed,
                                                   const float* scaling, int64_t* tree_idx_out, int32_t* win,
@@ -231,7 +233,7 @@ __global__ __launch_bounds__(MAXT) void k_sample(ReplayView v, int32_t batch, fl
     if (threadIdx.x == 0 && (int)blockIdx.x == noise_blocks + 1) g_stamp[6] = wall_clock64();
     if (threadIdx.x == 0 && blockIdx.x == gridDim.x - 1) g_stamp[7] = wall_clock64();
 #endif
-    rb_adam_hosted_block<AU>(adam_dev, (int)blockIdx.x - 1 - noise_blocks, (int)gridDim.x - 1 - noise_blocks, s_adam);
+    rb_adam_hosted_block<AU, EMA>(adam_dev, (int)blockIdx.x - 1 - noise_blocks, (int)gridDim.x - 1 - noise_blocks, s_adam);
 #if defined(RB_STAMP)
     __syncthreads();
     if (threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned long long*>(&g_stamp[8]), (unsigned long long)wall_clock64());

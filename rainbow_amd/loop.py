@@ -45,8 +45,8 @@ def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states,
             if on_eval is not None and eval_every and T % eval_every < S:         # main.py:166-170
                 on_eval(T)
                 agent.train()
-            if T % args.target_update < S:
-                agent.update_target_net()                                         # main.py:177-178
+            if T % args.target_update < S and not float(getattr(agent, "target_tau", 0.0)) > 0:
+                agent.update_target_net()                                         # main.py:177-178 (an EMA target follows every step instead)
     return learns
 
 
@@ -54,6 +54,8 @@ def train_device(agent, mem, env, args, T_max, on_eval=None, per_stream_noise=Fa
     """main.py:146-184 for S = env.streams device streams (INTEGRATION.md §2): T counts environment steps, S per round;
     reset_noise once per replay_frequency env steps; from learn_start on, beta is annealed by priority_weight_increase * S per
     round, one learn() per replay_frequency env steps (learn_owed), target update and evaluation at `T % k < S`.
+    With agent.target_tau > 0 (args.target_tau: the target follows every optimiser step by EMA) the periodic hard target update
+    is skipped.
     on_eval(T), if given, is called at the evaluation rounds (args.evaluation_interval); it may synchronise.
     per_stream_noise=True: every stream acts under its OWN noisy-net sample — agent.reset_noise_rows(S, rng=(args.seed, T)) at
     the cadence of reset_noise() (which stays: learn() needs the learner's own sample) and act_batch(per_row_noise=True);

@@ -10,7 +10,8 @@ games, unclipped returns), same output format.  `--multi-step` / `--learn-start`
 stratified draw needs more than batch_size * (multi_step + 1) * S stored transitions, and its last stratum must not fall inside
 the multi_step newest slots, which all carry the running max priority (Agent.learn raises; the line then ends in STOPPED).
 `--augment-pad P` turns the replay's random-shift augmentation on (ReplayMemory augment_pad: sampled stacks shifted by up to P
-pixels, the learn step on the gathered path)."""
+pixels, the learn step on the gathered path).  `--target-tau TAU` gives the agent an EMA target (Agent target_tau: the target follows
+every optimiser step inside the clip + Adam pass, and the loop makes no hard target syncs)."""
 import argparse
 import os
 import sys
@@ -26,22 +27,23 @@ sys.path.insert(0, ROOT)
 EVAL_SEED = 777_001
 
 
-def options(t_max, dev, multi_step=20, learn_start=1600, augment_pad=0):
+def options(t_max, dev, multi_step=20, learn_start=1600, augment_pad=0, target_tau=0.0):
     return types.SimpleNamespace(
-        augment_pad=augment_pad,
+        augment_pad=augment_pad, target_tau=target_tau,
         device=dev, architecture="data-efficient", hidden_size=256, multi_step=multi_step, learning_rate=1e-4, replay_frequency=1,
         target_update=2000, batch_size=32, atoms=51, V_min=-10.0, V_max=10.0, history_length=4, noisy_std=0.1, discount=0.99,
         priority_exponent=0.5, priority_weight=0.4, adam_eps=1.5e-4, norm_clip=10.0, reward_clip=1, learn_start=learn_start,
         model=None, T_max=t_max)
 
 
-def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", multi_step=20, learn_start=1600, augment_pad=0):
+def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", multi_step=20, learn_start=1600, augment_pad=0,
+        target_tau=0.0):
     from rainbow_amd.agent import Agent
     from rainbow_amd.envs import BreakoutVec, CatchVec
     from rainbow_amd.loop import evaluate_device, evaluate_vec, train_device
     from rainbow_amd.memory import ReplayMemory
     make = {"catch": CatchVec, "breakout": BreakoutVec}[game]
-    args = options(t_max, dev, multi_step, learn_start, augment_pad)
+    args = options(t_max, dev, multi_step, learn_start, augment_pad, target_tau)
     args.evaluation_interval = t_eval
     np.random.seed(seed)
     torch.manual_seed(np.random.randint(1, 10000))
@@ -87,13 +89,15 @@ def main():
     ap.add_argument("--multi-step", type=int, default=20)
     ap.add_argument("--learn-start", type=int, default=1600)
     ap.add_argument("--augment-pad", type=int, default=0)
+    ap.add_argument("--target-tau", type=float, default=0.0)
     a = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
     dev = torch.device("cuda", 0)
     for S in a.streams:
         for k in range(a.seeds if S == 1 else min(3, a.seeds)):
-            run(S, 101 + 7 * k, a.t_max, a.t_eval, not a.no_learn, dev, a.protocol, a.env, a.multi_step, a.learn_start, a.augment_pad)
+            run(S, 101 + 7 * k, a.t_max, a.t_eval, not a.no_learn, dev, a.protocol, a.env, a.multi_step, a.learn_start, a.augment_pad,
+                a.target_tau)
 
 
 if __name__ == "__main__":
