@@ -660,7 +660,7 @@ int rb_learner_train_step(rb_learner_t* l, const rb_train_step_t* a, rb_stream_t
  *   the other way round (the priorities were written back in call k's backward), so 30 us of pure HBM streaming run
  *   beside the sampler's one latency-bound workgroup instead of in front of it.  Same arithmetic in the same order: the
  *   parameters are bit-identical to the undeferred ones.  EVERY other learner entry point that touches parameters,
- *   moments, gradients or the norm (act, act_batch, learn*, clip_*, sync_target, set_target_tau, target_ema, finish_grads, debug_read) first runs the
+ *   moments, gradients or the norm (act, act_batch, learn*, clip_*, sync_target, set_target_tau, target_ema, shrink_perturb, finish_grads, debug_read) first runs the
  *   pending pass as a launch of its own, on the stream it is given — use ONE stream per handle.  A caller that reads the
  *   borrowed buffers itself (params_dev, exp_avg, exp_avg_sq, grads_dev, norm_dev) calls rb_learner_flush first.       */
 #define RB_LEARNER_FUSE_FC_H_DW 1
@@ -779,6 +779,23 @@ int rb_learner_sync_target(rb_learner_t* l, rb_stream_t stream);
  *   whose optimiser is not the library's (call it right after that optimiser's step).  tau = 0 does nothing.              */
 int rb_learner_set_target_tau(rb_learner_t* l, float tau, rb_stream_t stream);
 int rb_learner_target_ema(rb_learner_t* l, float tau, rb_stream_t stream);
+
+/* Shrink-and-perturb reset (the periodic resets of SR-SPR / BBF, which make a replay ratio above 1 work): per named tensor of
+ * rb_learner_param_layout   theta <- alpha * theta + (1 - alpha) * phi,   phi a FRESH draw from the tensor's initial distribution
+ * (convs.*: U(+-1/sqrt(fan_in)); *_mu: U(+-1/sqrt(in)); weight_sigma = noisy_std/sqrt(in) and bias_sigma = noisy_std/sqrt(out)
+ * are constants: phi is that constant).  convs.* take alpha_encoder, fc_* take alpha_head; both in [0, 1], anything else (NaN
+ * too) is RB_ERR_INVALID.  ONE launch over the flat buffers, in stream order, no synchronisation, no host draw.
+ *   A pending optimiser pass runs FIRST (it was computed for the old tensors).
+ *   phi of flat element i is word i & 3 of Philox4x32-10(key = seed ^ 0x5245534554, counter hi = draw, lo = i >> 2):
+ *     u = (float)(x >> 8) * 2^-24, phi = bound * (2u - 1), bound rounded to f32; new = alpha * theta + (1.0f - alpha) * phi as two
+ *     products and a sum.  It depends on (seed, draw, i) only: replicas that pass the same pair draw the same phi, and a resumed
+ *     run repeats it bit for bit.  The caller advances `draw` once per reset.
+ *   alpha == 1: the tensor and its moments are neither read nor written.  alpha == 0: phi is written without reading theta.
+ *   with_target != 0: the target parameters get the same rule with the SAME phi (alpha == 0: online and target bit-equal).
+ *   exp_avg_dev / exp_avg_sq_dev [n_params] (both or neither; NULL = no moments to clear): zeroed for every tensor with alpha < 1.
+ *   The alignment padding between the tensors is never written; gradients, noise, the step counter and the replay are untouched. */
+int rb_learner_shrink_perturb(rb_learner_t* l, float alpha_encoder, float alpha_head, float noisy_std, uint64_t seed, uint64_t draw,
+                              int32_t with_target, float* exp_avg_dev, float* exp_avg_sq_dev, rb_stream_t stream);
 
 /* White-box access for parity tests: copies an internal activation to out_dev.
  * what: 0 log_ps_a [B][atoms], 1 m (projected target) [B][atoms], 2 argmax a* i32[B],

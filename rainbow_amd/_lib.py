@@ -182,6 +182,7 @@ SIGNATURES = {
     "rb_learner_sync_target": (c_int, [c_void_p, c_void_p]),
     "rb_learner_set_target_tau": (c_int, [c_void_p, c_float, c_void_p]),
     "rb_learner_target_ema": (c_int, [c_void_p, c_float, c_void_p]),
+    "rb_learner_shrink_perturb": (c_int, [c_void_p, c_float, c_float, c_float, c_uint64, c_uint64, c_int32, c_void_p, c_void_p, c_void_p]),
     "rb_learner_get_rng": (c_int, [c_void_p, C.POINTER(c_uint64), C.POINTER(c_uint64), c_void_p]),
     "rb_learner_set_rng": (c_int, [c_void_p, c_uint64, c_uint64, c_void_p]),
     "rb_learner_debug_read": (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),

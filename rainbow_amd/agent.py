@@ -277,6 +277,13 @@ class Agent:
         tau = float(getattr(args, "target_tau", 0.0) or 0.0)
         if tau != 0.0:
             self.target_tau = tau
+        # shrink-and-perturb resets (reset_parameters): the defaults, the seed of the draws and the number of resets done so far,
+        # which is the `draw` word of the next one's Philox counter (checkpoint() / restore() carry it)
+        self._noisy_std = float(getattr(args, "noisy_std", 0.1))
+        enc, head = getattr(args, "reset_shrink_encoder", None), getattr(args, "reset_shrink_head", None)
+        self._reset_shrink = (0.5 if enc is None else float(enc), 0.0 if head is None else float(head))
+        self._reset_seed = int(getattr(args, "seed", 0) or 0)
+        self.resets = 0
 
     # The flat tensors the library borrows.  With a deferred optimiser pass pending they are one update behind: reading them
     # through these names runs the pass first.
@@ -324,6 +331,35 @@ class Agent:
         its own optimiser step, when the optimiser is not the library's (RAINBOW_AMD_FUSED_ADAM=0)."""
         L.check(self._lib, self._lib.rb_learner_target_ema(self._h, float(tau), self._stream()))
         self._update_pending = False
+
+    def reset_parameters(self, shrink_encoder=None, shrink_head=None, target=True, restart_step=False, rng=None):
+        """Shrink-and-perturb reset (include/rainbow_hip.h rb_learner_shrink_perturb), one launch in stream order and no
+        synchronisation: every tensor is pulled towards a FRESH draw phi from its initial distribution,
+        theta <- alpha * theta + (1 - alpha) * phi, with alpha = shrink_encoder for convs.* (default args.reset_shrink_encoder, 0.5
+        if absent) and alpha = shrink_head for the noisy-linear layers (default args.reset_shrink_head, 0.0 if absent: a full
+        re-initialisation); an alpha outside [0, 1] raises ValueError.  A pending optimiser pass runs first.  target=True: the
+        target network follows the same draw.  The Adam moments of the touched tensors (alpha < 1) are cleared — those of
+        whichever optimiser is active; restart_step=True also sets the Adam step number back to 0 (the default leaves it alone).
+        rng = (seed, draw) keys the draw and defaults to (args.seed or 0, self.resets): replicas that pass the same pair draw
+        the same phi, and a run resumed from checkpoint() repeats it bit for bit.  self.resets counts the resets done."""
+        ae = self._reset_shrink[0] if shrink_encoder is None else float(shrink_encoder)
+        ah = self._reset_shrink[1] if shrink_head is None else float(shrink_head)
+        for name, a in (("shrink_encoder", ae), ("shrink_head", ah)):
+            if not 0.0 <= a <= 1.0:                       # (also NaN)
+                raise ValueError("reset_parameters: %s must be in [0, 1], got %r" % (name, a))
+        seed, draw = (self._reset_seed, self.resets) if rng is None else (int(rng[0]), int(rng[1]))
+        st = self.optimiser.state.get(self._params, {})   # (torch's own Adam has no state before its first step: no moments to clear)
+        m, v = st.get("exp_avg"), st.get("exp_avg_sq")
+        L.check(self._lib, self._lib.rb_learner_shrink_perturb(
+            self._h, ae, ah, self._noisy_std, seed & 0xFFFFFFFFFFFFFFFF, draw & 0xFFFFFFFFFFFFFFFF, 1 if target else 0,
+            m.data_ptr() if m is not None else None, v.data_ptr() if v is not None else None, self._stream()))
+        self._update_pending = False                      # (the library ran a pending pass first)
+        if restart_step:
+            if self._step_dev is not None:
+                self._step_dev.zero_()
+            if "step" in st:
+                st["step"].zero_()
+        self.resets += 1
 
     def flush(self):
         """Run the optimiser pass the last learn() left pending (RAINBOW_AMD_DEFER_UPDATE), if any."""
@@ -866,7 +902,8 @@ class Agent:
     def checkpoint(self, path=None):
         """Everything the learner needs to continue bit-for-bit: online / target parameters (a pending optimiser pass, which
         with target_tau > 0 moves the target too, has run before they are copied), target_tau, both noise buffers, Adam
-        moments + step, the Philox (seed, epoch) of the noise generator and the pending-resample flag.  The reference's
+        moments + step, the Philox (seed, epoch) of the noise generator, the pending-resample flag and the number of resets done
+        (reset_parameters: the next reset's draw).  The reference's
         save() (weights only, agent.py:106-107) stays what main.py:182 calls; this is the superset a resumable run needs
         (main.py has no such thing: it restarts the optimiser).  Returns the dict; writes it with torch.save if `path`."""
         if not isinstance(self.optimiser, _FlatAdam):
@@ -880,7 +917,7 @@ class Agent:
                   noise=self.noise.cpu(), target_noise=self.target_noise.cpu(), exp_avg=st["exp_avg"].cpu(),
                   exp_avg_sq=st["exp_avg_sq"].cpu(), adam_step=float(st["step"]), rng_seed=int(seed.value),
                   rng_epoch=int(epoch.value), noise_pending=bool(self._noise_pending), training=bool(self.training),
-                  target_tau=float(self._target_tau))
+                  target_tau=float(self._target_tau), resets=int(self.resets))
         if path is not None:
             torch.save(ck, path)
         return ck
@@ -911,6 +948,7 @@ class Agent:
         self._noise_jobs = {}
         if "target_tau" in ck:                      # (checkpoints from before the EMA target carry none: the agent keeps its own)
             self.target_tau = ck["target_tau"]
+        self.resets = int(ck.get("resets", 0))      # (none before reset_parameters existed: no reset has been done)
 
     def save(self, path, name="model.pth"):
         torch.save(self.state_dict(), os.path.join(path, name))

@@ -31,6 +31,7 @@
 #include "conv_dispatch.h"
 #include "fc_dispatch.h"
 #include "optimizer_host.h"
+#include "param_reset.h"
 #include "act_host.h"
 #include "exchange_host.h"
 #include "layout_api.h"

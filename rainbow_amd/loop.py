@@ -26,6 +26,8 @@ def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states,
     seed = int(getattr(args, "seed", 0))
     increase = (1 - args.priority_weight) / (T_max - args.learn_start)           # main.py:123
     eval_every = int(getattr(args, "evaluation_interval", 0) or 0)
+    replay_ratio = float(getattr(args, "replay_ratio", 0) or 0)                   # learn steps per environment step; may exceed 1
+    reset_interval = int(getattr(args, "reset_interval", 0) or 0)                 # in GRADIENT steps; 0 = never
     learn_owed, learns = 0.0, 0
     if per_stream_noise:
         agent.reset_noise_rows(S, rng=(seed, 0))                                  # S < replay_frequency: the first rounds come before the first redraw
@@ -37,11 +39,13 @@ def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states,
         states = round_fn(states)                                                 # main.py:153-157
         if T >= args.learn_start:
             mem.priority_weight = min(mem.priority_weight + increase * S, 1)      # main.py:161
-            learn_owed += S / args.replay_frequency
+            learn_owed += S * replay_ratio if replay_ratio > 0 else S / args.replay_frequency
             while learn_owed >= 1:
                 agent.learn(mem)                                                  # main.py:164
                 learn_owed -= 1
                 learns += 1
+                if reset_interval and learns % reset_interval == 0:
+                    agent.reset_parameters()                                      # shrink-and-perturb (Agent.reset_parameters)
             if on_eval is not None and eval_every and T % eval_every < S:         # main.py:166-170
                 on_eval(T)
                 agent.train()
@@ -56,6 +60,10 @@ def train_device(agent, mem, env, args, T_max, on_eval=None, per_stream_noise=Fa
     round, one learn() per replay_frequency env steps (learn_owed), target update and evaluation at `T % k < S`.
     With agent.target_tau > 0 (args.target_tau: the target follows every optimiser step by EMA) the periodic hard target update
     is skipped.
+    args.replay_ratio (absent or 0: replay_frequency decides, as above): learn steps per environment step, a float that may exceed
+    1 — S * replay_ratio learn steps are owed per round.  args.reset_interval (absent or 0: never) counts GRADIENT steps: right
+    after the learn() that makes the count a multiple of it, agent.reset_parameters() shrinks and perturbs the networks
+    (args.reset_shrink_encoder / reset_shrink_head) — what keeps a replay ratio above 1 from hurting.
     on_eval(T), if given, is called at the evaluation rounds (args.evaluation_interval); it may synchronise.
     per_stream_noise=True: every stream acts under its OWN noisy-net sample — agent.reset_noise_rows(S, rng=(args.seed, T)) at
     the cadence of reset_noise() (which stays: learn() needs the learner's own sample) and act_batch(per_row_noise=True);
@@ -100,8 +108,9 @@ def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None, per_strea
     the ACTOR: after a lost life env.py's deque also holds the ending step's observation below the no-op screen, here the
     stream's stack moves by one frame per round, so that frame is skipped.
     Cadences are train_device's: reset_noise once per replay_frequency env steps; from learn_start on, beta annealed by
-    priority_weight_increase * S per round, one learn() per replay_frequency env steps (learn_owed), target update and on_eval
-    at `T % k < S`.  per_stream_noise: as in train_device (one noise sample per emulator).  Returns the number of learn() calls made."""
+    priority_weight_increase * S per round, one learn() per replay_frequency env steps (learn_owed) — or S * args.replay_ratio
+    per round, with agent.reset_parameters() every args.reset_interval gradient steps, as in train_device — target update and
+    on_eval at `T % k < S`.  per_stream_noise: as in train_device (one noise sample per emulator).  Returns the number of learn() calls made."""
     S = len(emus)
     if S != mem.streams or S != front.streams:
         raise ValueError("train_host_vec: %d emulators, a front end of %d streams, a memory of %d" % (S, front.streams, mem.streams))

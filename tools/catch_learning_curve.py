@@ -11,7 +11,10 @@ stratified draw needs more than batch_size * (multi_step + 1) * S stored transit
 the multi_step newest slots, which all carry the running max priority (Agent.learn raises; the line then ends in STOPPED).
 `--augment-pad P` turns the replay's random-shift augmentation on (ReplayMemory augment_pad: sampled stacks shifted by up to P
 pixels, the learn step on the gathered path).  `--target-tau TAU` gives the agent an EMA target (Agent target_tau: the target follows
-every optimiser step inside the clip + Adam pass, and the loop makes no hard target syncs)."""
+every optimiser step inside the clip + Adam pass, and the loop makes no hard target syncs).  `--replay-ratio R` makes R learn steps
+per environment step (args.replay_ratio; the recipe's replay_frequency = 1 is ratio 1) and `--reset-interval N` shrinks and perturbs
+the networks every N GRADIENT steps (args.reset_interval: Agent.reset_parameters with its defaults, encoder 0.5 / head 0); the line
+then carries both and the number of resets done."""
 import argparse
 import os
 import sys
@@ -27,9 +30,9 @@ sys.path.insert(0, ROOT)
 EVAL_SEED = 777_001
 
 
-def options(t_max, dev, multi_step=20, learn_start=1600, augment_pad=0, target_tau=0.0):
+def options(t_max, dev, multi_step=20, learn_start=1600, augment_pad=0, target_tau=0.0, replay_ratio=0.0, reset_interval=0):
     return types.SimpleNamespace(
-        augment_pad=augment_pad, target_tau=target_tau,
+        augment_pad=augment_pad, target_tau=target_tau, replay_ratio=replay_ratio, reset_interval=reset_interval,
         device=dev, architecture="data-efficient", hidden_size=256, multi_step=multi_step, learning_rate=1e-4, replay_frequency=1,
         target_update=2000, batch_size=32, atoms=51, V_min=-10.0, V_max=10.0, history_length=4, noisy_std=0.1, discount=0.99,
         priority_exponent=0.5, priority_weight=0.4, adam_eps=1.5e-4, norm_clip=10.0, reward_clip=1, learn_start=learn_start,
@@ -37,14 +40,15 @@ def options(t_max, dev, multi_step=20, learn_start=1600, augment_pad=0, target_t
 
 
 def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", multi_step=20, learn_start=1600, augment_pad=0,
-        target_tau=0.0):
+        target_tau=0.0, replay_ratio=0.0, reset_interval=0):
     from rainbow_amd.agent import Agent
     from rainbow_amd.envs import BreakoutVec, CatchVec
     from rainbow_amd.loop import evaluate_device, evaluate_vec, train_device
     from rainbow_amd.memory import ReplayMemory
     make = {"catch": CatchVec, "breakout": BreakoutVec}[game]
-    args = options(t_max, dev, multi_step, learn_start, augment_pad, target_tau)
+    args = options(t_max, dev, multi_step, learn_start, augment_pad, target_tau, replay_ratio, reset_interval)
     args.evaluation_interval = t_eval
+    args.seed = seed
     np.random.seed(seed)
     torch.manual_seed(np.random.randint(1, 10000))
     env = make(S, dev, seed=seed)
@@ -71,7 +75,10 @@ def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", mul
     except RuntimeError as e:
         note = "  STOPPED: " + str(e)[:150]
     torch.cuda.synchronize()
-    print("S %2d seed %3d %s (%.1f s): " % (S, seed, "learn" if learn else "NO-LEARN", time.perf_counter() - t0)
+    tag = "learn" if learn else "NO-LEARN"
+    if replay_ratio or reset_interval:
+        tag += " replay-ratio %g reset-interval %d (%d resets)" % (replay_ratio or 1.0, reset_interval, agent.resets)
+    print("S %2d seed %3d %s (%.1f s): " % (S, seed, tag, time.perf_counter() - t0)
           + " ".join("%d:%+.3f" % c for c in curve) + "  training-episode mean %+.3f" % env.stats()["mean_return"] + note,
           flush=True)
     env.close()
@@ -90,6 +97,8 @@ def main():
     ap.add_argument("--learn-start", type=int, default=1600)
     ap.add_argument("--augment-pad", type=int, default=0)
     ap.add_argument("--target-tau", type=float, default=0.0)
+    ap.add_argument("--replay-ratio", type=float, default=0.0)
+    ap.add_argument("--reset-interval", type=int, default=0)
     a = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
@@ -97,7 +106,7 @@ def main():
     for S in a.streams:
         for k in range(a.seeds if S == 1 else min(3, a.seeds)):
             run(S, 101 + 7 * k, a.t_max, a.t_eval, not a.no_learn, dev, a.protocol, a.env, a.multi_step, a.learn_start, a.augment_pad,
-                a.target_tau)
+                a.target_tau, a.replay_ratio, a.reset_interval)
 
 
 if __name__ == "__main__":
