@@ -1,11 +1,11 @@
 // Agent.act / evaluate_q (agent.py:53-55, 110-112; main.py:153, test.py:26,39): the forward of ONE un-batched
-// state.  The training kernels (conv_fwd.h, noisy_linear.h) are shaped for 96 images: with one image they run 2-3
+// state.  The training kernels (conv_fwd.h, nl_fwd.h) are shaped for 96 images: with one image they run 2-3
 // workgroups per layer and cost the same 14 us as with 96 (a pure staging-latency chain).  This path trades MFMA for
 // breadth instead: one output channel (conv) or one weight row per wave (noisy linear), hundreds of small
 // workgroups, weights read as wave-uniform scalars / one coalesced sweep, so a layer is one memory round trip.
 // Same arithmetic as model.py:42-46,69-80 (f32, fused multiply-add accumulation in a fixed order).
 #pragma once
-#include "noisy_linear.h"
+#include "nl_common.h"
 #include "rb_common.h"
 #include "rb_device.h"
 #include "kernel_stamp.h"

@@ -2,13 +2,14 @@
 // Included by learner.hip only (non-template kernels, and rb_launch_adam_pending, which is defined here).
 #pragma once
 #include "learner_internal.h"
+#include "nl_dw.h"
 
 // (ClipAdamArgs, rb_adam_elem / rb_adam_quad and the hosted form of the pass: adam_body.h)
 // Tile part of the fused optimiser pass (batch <= 32).  The hidden layer's weight gradient is a rank-B product,
 // g_mu = dY^T X  (dY [B][2H], X [B][F], both L2-resident: 0.5 MB), g_sigma = g_mu * (eps_out x eps_in).  Writing it in the
 // backward and reading it back here costs 2 x 25.7 MB of HBM traffic per step; instead a wave recomputes its 16 x 64
-// tile with 32 MFMAs (same operand order as rb_nl_dw_body_pipe, so the bits equal those of the backward's norm-only
-// pass) while its p / m / v loads are in flight, and applies clip + Adam to mu and sigma right there: 6 array passes
+// tile with 32 MFMAs (nl_dw.h's tile setup and MFMA block, the ones the backward's norm-only pass ran: the same bits)
+// while its p / m / v loads are in flight, and applies clip + Adam to mu and sigma right there: 6 array passes
 // over the 6.4 M weights instead of 9.
 struct FusedDwAdamArgs {
   NlDwArgs dw;                 // operands of the weight gradient (g_* unused)
@@ -22,69 +23,43 @@ struct FusedDwAdamArgs {
 template <bool WT>
 __device__ __forceinline__ void rb_fused_dw_adam_tile(const ClipAdamArgs& a, const FusedDwAdamArgs& f, int b2, float coef) {
   const NlDwArgs& d = f.dw;
-  const int lane = rb_lane(), wave = rb_wave();
   const int which = b2 & 1, b = b2 >> 1;                 // 0: mu, 1: sigma
-  const int bx = b % f.dw_x, by = b / f.dw_x;
-  const int kt = bx * 256 + wave * 64;
-  if (kt >= d.K) return;                                  // wave-uniform
-  const int g = (d.n_prob > 1 && by >= d.prob[1].tile_begin) ? 1 : 0;
-  const NlDwProblem pr = d.prob[g];
-  const int row0 = pr.row_begin + (by - pr.tile_begin) * 16;
-  const int row_end = pr.row_begin + pr.row_cnt;
-  const int c = lane & 15, q = lane >> 4;
-  int col4 = kt + 4 * c;
-  const bool cv = col4 < d.K;
-  if (!cv) col4 = d.K - 4;
-  int arow = row0 + c;
-  const bool av_ok = arow < row_end;
-  if (!av_ok) arow = row_end - 1;
+  const NlDwTile t = rb_nl_dw_tile(d, b % f.dw_x, b / f.dw_x, 256);
+  if (!t.live) return;                                    // wave-uniform (no norm slot to zero here)
+  const int col4 = t.col4(t.kt);
+  const bool cv = t.col_ok(t.kt);
   const int64_t arr = which ? f.sigma_off : f.mu_off;
   // operands of the gradient tile first (they gate the MFMAs), then the 12 parameter / moment quads (they gate the update)
   float avs[8];
   float4 xs[8];
 #pragma unroll
-  for (int st = 0; st < 8; ++st) {
-    const int m = 4 * st + q;
+  for (int st = 0; st < 8; ++st) {                        // this tile zeroes the quad it loaded
+    const int m = 4 * st + t.q;
     const bool mv = m < d.M;
-    const int mcl = mv ? m : d.M - 1;
-    avs[st] = (mv && av_ok) ? d.dy[(int64_t)mcl * d.ldy + arow] : 0.0f;
-    xs[st] = rb_ld4(d.x + (int64_t)mcl * d.ldx + pr.x_off + col4);
+    avs[st] = t.dy_masked(d.dy, d.ldy, m, d.M);
+    xs[st] = rb_ld4(d.x + (int64_t)(mv ? m : d.M - 1) * d.ldx + t.pr.x_off + col4);
     if (!mv) { xs[st].x = 0.0f; xs[st].y = 0.0f; xs[st].z = 0.0f; xs[st].w = 0.0f; }
   }
-  const float4 e4 = rb_ld4(d.ein + pr.ein_off + col4);
+  const float4 e4 = rb_ld4(d.ein + t.pr.ein_off + col4);
   float eo4[4];
   int64_t off[4];
   float4 P[4], M[4], V[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    int n = row0 + 4 * q + e;
-    if (n > row_end - 1) n = row_end - 1;                 // clamped rows are loaded (legal) and never stored
+    const int n = t.row_clamped(e);                       // clamped rows are loaded (legal) and never stored
     eo4[e] = d.eout[n];
     off[e] = arr + (int64_t)n * d.K + col4;
     P[e] = rb_ld4(a.p + off[e]); M[e] = rb_ld4(a.m + off[e]); V[e] = rb_ld4(a.v + off[e]);
   }
-  rb_f32x4 acc[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { acc[0][e] = 0.0f; acc[1][e] = 0.0f; acc[2][e] = 0.0f; acc[3][e] = 0.0f; }
-#pragma unroll
-  for (int st = 0; st < 8; ++st) {
-    if (4 * st < d.M) {                                   // uniform
-      acc[0] = rb_mfma16(avs[st], xs[st].x, acc[0]);
-      acc[1] = rb_mfma16(avs[st], xs[st].y, acc[1]);
-      acc[2] = rb_mfma16(avs[st], xs[st].z, acc[2]);
-      acc[3] = rb_mfma16(avs[st], xs[st].w, acc[3]);
-    }
-  }
+  rb_f32x4 acc[4], accb;                                  // (no bias sum here: accb stays unused)
+  rb_nl_dw_zero(acc, accb);
+  rb_nl_dw_mfma32(0, d.M, [&](int st) { return avs[st]; }, [&](int st) { return xs[st]; }, false, acc, accb);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const int n = row0 + 4 * q + e;
-    if (n < row_end && cv) {
+    if (t.row(e) < t.row_end && cv) {
       float4 gr;
       gr.x = acc[0][e]; gr.y = acc[1][e]; gr.z = acc[2][e]; gr.w = acc[3][e];
-      if (which) {                                        // block-uniform: g_sigma = g_mu * (eps_out * eps_in), model.py:39,44
-        const float eo = eo4[e];
-        gr.x = gr.x * (eo * e4.x); gr.y = gr.y * (eo * e4.y); gr.z = gr.z * (eo * e4.z); gr.w = gr.w * (eo * e4.w);
-      }
+      if (which) gr = rb_noisy_grad4(gr, eo4[e], e4);     // block-uniform: g_sigma = g_mu * (eps_out * eps_in), model.py:39,44
       rb_adam_quad(P[e], gr, M[e], V[e], coef, a);
       if (WT) {
         const unsigned o = (unsigned)(4 * off[e]);
@@ -201,10 +176,7 @@ __global__ __launch_bounds__(256) void k_materialize_sigma(float* g, int64_t mu4
     const int row = (int)(j / f4), cq = (int)(j - (int64_t)row * f4);
     const float eo = eout[row];
     const float4 e = rb_ld4(ein + 4 * (int64_t)(cq + (row >= split_row ? f4 : 0)));
-    const float4 gm = rb_ld4(g + 4 * (mu4 + j));
-    float4 gs;
-    gs.x = gm.x * (eo * e.x); gs.y = gm.y * (eo * e.y); gs.z = gm.z * (eo * e.z); gs.w = gm.w * (eo * e.w);
-    rb_st4(g + 4 * (mu4 + len4 + j), gs);
+    rb_st4(g + 4 * (mu4 + len4 + j), rb_noisy_grad4(rb_ld4(g + 4 * (mu4 + j)), eo, e));
   }
 }
 

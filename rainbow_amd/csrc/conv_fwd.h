@@ -26,7 +26,7 @@ struct ConvLdsFwdArgs {
   ImgSrc src;                // FIRST layer input
   const float* in_f;         // later layers: [img][cin][IP]
   float* out;                // [img][cout][P]
-  float* out_blocked;        // optional second copy of the flattened output in the k-blocked layout of noisy_linear.h
+  float* out_blocked;        // optional second copy of the flattened output in the k-blocked layout of nl_fwd.h
   int rows_total;            //   ... with this many rows (images)
   int ipb;                   // k_conv_fwd_multi_t16 / k_conv_fwd_full: images per workgroup
   int img_fast;              // k_conv_fwd_lds: grid = (images, cout tiles, position chunks) — the image is the fastest block index

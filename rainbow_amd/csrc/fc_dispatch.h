@@ -48,8 +48,8 @@ static int fc_forward(rb_learner* l, int n_on, int n_tg, const NetPtrs& on, cons
     RB_LAUNCH(k_block_copy, dim3((unsigned)rb_div_up((int64_t)NI * L.F, 256)), dim3(256), stream, feat, NI, L.F, l->feat_b);
     RB_LAUNCH_CHECK();
   }
-  // hidden layer: both streams, both nets, weights streamed once, bias + ReLU fused, no partials (noisy_linear.h)
-  NlFwd2Args a;
+  // hidden layer: both streams, both nets, weights streamed once, bias + ReLU fused, no partials (nl_fwd.h)
+  NlFwdArgs a;
   a.x = l->feat_b;
   a.m_base[0] = 0; a.m_cnt[0] = n_on; a.m_base[1] = n_on; a.m_cnt[1] = n_tg;
   a.w[0] = nl_h(on); a.w[1] = nl_h(tg);
@@ -72,7 +72,7 @@ static int fc_forward(rb_learner* l, int n_on, int n_tg, const NetPtrs& on, cons
   }
   RB_LAUNCH_CHECK();
   // output layer: value rows read h[:, :H], advantage rows read h[:, H:]; bias fused
-  NlFwd2Args z;
+  NlFwdArgs z;
   z.x = l->h_b;
   z.m_base[0] = 0; z.m_cnt[0] = n_on; z.m_base[1] = n_on; z.m_cnt[1] = n_tg;
   z.w[0] = nl_z(on); z.w[1] = nl_z(tg);

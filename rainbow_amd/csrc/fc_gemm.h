@@ -1,6 +1,6 @@
 // fc_gemm.h — the hidden NoisyLinear layer (model.py:42-46, 56-63) as LDS-tiled f32 MFMA GEMMs for LARGE batches.
 //
-// noisy_linear.h streams every weight tile through registers once per 16..64 batch rows: right when the batch is 32 (the
+// nl_fwd.h / nl_bwd.h stream every weight tile through registers once per 16..64 batch rows: right when the batch is 32 (the
 // layer is a weight-bandwidth problem there), wrong at batch 256, where M = 768 forward rows make it a 4.9 GFLOP
 // contraction: the streamed kernels re-read each weight tile 3.5 times (234 / 194 MB per launch for 67 / 56 MB of
 // tensors, PMC) and sit at 0.46 / 0.32 of the f32 MFMA roofline.  Here a workgroup owns a 128 x 128 output tile, walks the
@@ -27,9 +27,10 @@
 // trip with nothing to multiply, tools/stamp/gemm_timeline.py).  Epilogues pass the finished tile through LDS once so that every global store is a
 // 16-byte store of a row segment (512 contiguous bytes per 32 lanes) instead of 32 dword stores per thread.
 // Preconditions (host): K % 32 == 0, leading dimensions and offsets multiples of 4 floats, both streams of the layer read
-// the same input columns (the hidden layer; the output layer keeps noisy_linear.h).
+// the same input columns (the hidden layer; the output layer keeps the streamed kernels).
 #pragma once
-#include "noisy_linear.h"
+#include "nl_fwd.h"
+#include "nl_bwd.h"
 #include "kernel_stamp.h"
 
 #define RB_TG_T 128
@@ -173,7 +174,7 @@ __device__ __forceinline__ float4 rb_sel4(bool keep, float4 v) { return keep ? v
 
 // ================================================================================ forward ==
 struct FcGemmFwdArgs {
-  NlFwd2Args f;              // the same problem description as k_nl_fwd3 (x k-blocked; both nets; both row groups)
+  NlFwdArgs f;              // the same problem description as k_nl_fwd3 (x k-blocked; both nets; both row groups)
   int mt[2];                 // 128-row tiles of each net
   int nt;                    // 128-column tiles (over all weight rows of both streams)
   int S;                     // K splits per tile (<= 8)
@@ -187,7 +188,7 @@ struct FcFwdRegs { float4 x[2], mu[2], sg[2], ei[2]; };
 __global__ __launch_bounds__(RB_TG_THREADS) void k_fc_gemm_fwd(FcGemmFwdArgs g) {
   __shared__ __attribute__((aligned(16))) float lds[RB_TG_LDS];
   __shared__ int s_flag;
-  const NlFwd2Args& a = g.f;
+  const NlFwdArgs& a = g.f;
   const int lane = rb_lane(), wave = rb_wave(), tid = (int)threadIdx.x;
   const int wm = wave & 3, wn = wave >> 2;
   const int combos = g.nt * g.S;
@@ -510,14 +511,11 @@ __device__ __forceinline__ void rb_fc_gemm_dw(const NlDwArgs& a, int ntile, int 
       sq = fmaf(gbs, gbs, sq);
     }
   }
-  if (a.sq_part) {
-    sq = rb_wave_sum(sq);
-    if (lane == 0) a.sq_part[slot_base + wave] = sq;
-  }
+  rb_nl_sq_commit(a.sq_part, slot_base, sq);
 }
 
 // ---- the same weight gradient for the REPLICA EXCHANGE (rb_learner_finish_grads): the reduction rows are the gathered
-// factor blocks of M / rpb ranks (noisy_linear.h NlDwArgs: rpb, bstride, noise_blocks), and every rank's gradient is noisy with ITS
+// factor blocks of M / rpb ranks (nl_dw.h NlDwArgs: rpb, bstride, noise_blocks), and every rank's gradient is noisy with ITS
 // OWN epsilon:  g_mu = (1 / world) sum_r acc_r,  g_sigma = (1 / world) sum_r acc_r * (eps_out_r[n] * eps_in_r[k]),  acc_r = dY_r^T X_r.
 // rb_nl_dw_body_ranks does this one 16 x 64 tile per wave: at config 5's size (M = 8 x 32 rows, [1024 x 3136] weights) every
 // 16-row tile re-reads all of X — 0.5 GB of L2 traffic, 58 us per launch (profiles/round6_experiments.txt).  Here a workgroup owns
@@ -688,10 +686,7 @@ __device__ __forceinline__ void rb_fc_gemm_dw_ranks(const NlDwArgs& a, int ntile
     sq = fmaf(b0, b0, sq);
     sq = fmaf(b1, b1, sq);
   }
-  if (a.sq_part) {
-    sq = rb_wave_sum(sq);
-    if (lane == 0) a.sq_part[slot_base + wave] = sq;
-  }
+  rb_nl_sq_commit(a.sq_part, slot_base, sq);
 }
 
 #if defined(RB_HOST_INTERP)

@@ -2,6 +2,7 @@
 // finishing launches, the global-norm clip.  Included by learner.hip only (non-template kernels).
 #pragma once
 #include "learner_internal.h"
+#include "nl_dw.h"
 
 // ----------------------------------------------------------- small fused passes --
 // h[img][n] = relu(sum_s part[s][img][n] + (bias_mu + bias_sigma*eps_out)[n])        model.py:44,72-73

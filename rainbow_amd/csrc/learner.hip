@@ -6,7 +6,7 @@
 // issues ~1750 framework ops per learn(); here the step is a fixed chain of 14 launches after the sampler
 // (DESIGN.md §3 has the table with what bounds each):
 //   conv fwd x L (conv_fwd.h: operands in LDS, 8 waves split K)
-//   -> fc_h, fc_z forward (noisy_linear.h k_nl_fwd3: weights streamed once, whole K per block, no partials)
+//   -> fc_h, fc_z forward (nl_fwd.h k_nl_fwd3: weights streamed once, whole K per block, no partials)
 //   -> head (dueling + softmaxes + double-Q + projection + loss + dlogits, one workgroup per sample, atom bins in LDS)
 //   -> fc_z backward (dW || dX in one launch) -> fc_h backward (dW || dX || the sum-tree priority write-back)
 //   -> dfeat finish -> conv dX x (L-1) -> every conv dW in one launch -> slice reduction

@@ -8,7 +8,8 @@
 #include "noise_body.h"
 #include "adam_body.h"
 #include "learner_problems.h"
-#include "noisy_linear.h"
+#include "nl_fwd.h"
+#include "nl_bwd.h"
 #include "fc_gemm.h"
 #include "act_path.h"
 #include "rb_common.h"

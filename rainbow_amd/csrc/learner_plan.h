@@ -31,7 +31,7 @@ static LearnerCaps plan_caps(const Layout& L, const RbOpts& opt) {
   memset(&c, 0, sizeof(c));
   const int B = L.B;
   const int generic = opt.generic;
-  c.fast_fc = (L.F % 32 == 0 && L.H % 32 == 0 && L.F <= RB_FWD2_KMAX && L.H <= RB_FWD2_KMAX && generic == 0) ? 1 : 0;
+  c.fast_fc = (L.F % 32 == 0 && L.H % 32 == 0 && L.F <= RB_NL_FWD_KMAX && L.H <= RB_NL_FWD_KMAX && generic == 0) ? 1 : 0;
   c.fast_conv = (L.hist <= 4 && generic != 1) ? 1 : 0;
   // split-K factors: aim for >= ~2 workgroups per CU on the 256-CU part
   if (c.fast_fc) {
@@ -363,7 +363,7 @@ static FcFwdPlan plan_fc_fwd(const PlanIn& in, int n_on, int n_tg) {
   // batch 256: 64-row m-chunks halve the passes over the weights (at batch 32 one 64-row chunk for the online net's rows
   // reads every tile once instead of twice and is 7 us per step SLOWER: a workgroup's MFMAs are serial on its CU)
   const bool wide = m_max >= 128;
-  const unsigned mch32 = (unsigned)rb_div_up(m_max, wide ? 64 : RB_FWD2_MROWS);
+  const unsigned mch32 = (unsigned)rb_div_up(m_max, wide ? 64 : RB_NL_FWD_MROWS);
   // (16-row m-chunks — 384 workgroups, every CU busy — measured 20.8 us against 16.2: the tiles are re-read four times)
   p.hgrid = dim3((unsigned)(2 * ht16), 1, 2 * mch32); p.hblock = 64 * RB_NL_FWD_WAVES;
   p.h_kernel = wide ? FC_FWD_NL3_4 : FC_FWD_NL3_2;
@@ -492,7 +492,7 @@ static FcBwdPlan plan_fc_bwd(const PlanIn& in, bool spec) {
   p.norm_slots = p.fuse_norm ? p.z.slots + p.h.slots + p.c_slots : 0;
   p.norm_conv_base = p.z.slots + p.h.slots;
   const int vt = (int)rb_div_up(L.Z, 16), at = (int)rb_div_up(L.NZ - L.Z, 16);
-  // the output layer's input gradient with eight waves per workgroup (noisy_linear.h rb_nl_dx_body_tall) at batch <= 32
+  // the output layer's input gradient with eight waves per workgroup (nl_dx.h rb_nl_dx_body_tall) at batch <= 32
   // on 32-column tiles (H % 32 == 0: fast_fc): twice the workgroups, half the weight bytes through each CU
   p.z_tall = B <= 32;
   p.zg = NlBwdGrid{exch ? 0 : p.z.dw_x, exch ? 0 : vt + at, (int)rb_div_up(L.H, p.z_tall ? 32 : 64), 1, 2 * (int)rb_div_up(B, 64),

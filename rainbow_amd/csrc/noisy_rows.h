@@ -2,7 +2,7 @@
 // streams of a vectorised actor each explore with their own perturbation of the weights.  Included by learner.hip only.
 //
 // With per-row noise the weight W[m] = mu + sigma * (eps_out[m] eps_in[m]^T) differs for every row m, so the streamed kernels of
-// noisy_linear.h (which form W once in registers and share it over the rows) cannot serve it; a loop over rows would read the 51 MB
+// nl_fwd.h (which form W once in registers and share it over the rows) cannot serve it; a loop over rows would read the 51 MB
 // of the hidden layer's mu | sigma n times.  The factorised form reads them once:
 //
 //   y[m][j] = sum_k x[m][k] mu[j][k]  +  eo[m][j] * sum_k (x[m][k] ein[m][k]) sigma[j][k]  +  bmu[j] + bsigma[j] eo[m][j]
@@ -13,13 +13,13 @@
 // giving up weight sharing.  Measured against the per-row oracle in f32: at most 0.27 of the act tolerance.
 //
 // k_nlr_fwd keeps k_nl_fwd3's structure (line-wide buffer loads of the weight tiles, a per-wave LDS transpose to the operand
-// layout, waves splitting K and meeting once in LDS); eps_in is never staged in LDS (n = 64 rows of K = 3136 would be 800 KB) —
+// layout, waves splitting K and meeting once in LDS) and shares its per-wave setup (nl_fwd.h NlFwdWave); eps_in is never staged in LDS (n = 64 rows of K = 3136 would be 800 KB) —
 // the scaled activations arrive k-blocked (rb_blocked_index) from the pass in front: k_block_copy_rows for the hidden layer, the
 // hidden kernel's own epilogue for the output layer.  The accumulators and the cross-wave reduction buffer are twice fwd3's, so
 // the M tile stops at MT = 2 (32 rows per workgroup: 32 KB of reduction buffer + 36 KB of transpose tiles, 24 float4 of
 // activations in flight per lane); more rows are more m-chunks, as in the shared-noise path below 128 rows.
 #pragma once
-#include "noisy_linear.h"
+#include "nl_fwd.h"
 #include "noise_body.h"
 
 // ------------------------------------------------------------------ the generator --
@@ -98,7 +98,7 @@ struct NlRowsArgs {
 template <int MT>
 __global__ __launch_bounds__(64 * RB_NL_FWD_WAVES) void k_nlr_fwd(NlRowsArgs a) {
   __shared__ float s_red[RB_NL_FWD_WAVES][8 * MT][64];   // slots [0, 4 MT): the mu sums, [4 MT, 8 MT): the sigma sums
-  __shared__ __attribute__((aligned(16))) float s_wt[RB_NL_FWD_WAVES][2][16 * RB_FWD2_WT_LD];
+  __shared__ __attribute__((aligned(16))) float s_wt[RB_NL_FWD_WAVES][2][16 * RB_NL_FWD_WT_LD];
   const int lane = rb_lane(), wave = rb_wave();
   const int M = a.M;
   const int m0 = (int)blockIdx.z * (16 * MT);
@@ -108,34 +108,16 @@ __global__ __launch_bounds__(64 * RB_NL_FWD_WAVES) void k_nlr_fwd(NlRowsArgs a) 
   const int row0 = grp.row_begin + ((int)blockIdx.x - grp.tile_begin) * 16;
   const int row_end = grp.row_begin + grp.row_cnt;
   const int K = a.K;
-  const int nblk = K / 32;                               // host guarantees K % 32 == 0
-  const int base_n = nblk / RB_NL_FWD_WAVES, extra = nblk % RB_NL_FWD_WAVES;
-  const int nsc = rb_wave_uniform(base_n + (wave < extra ? 1 : 0));                     // 32-wide blocks of this wave
-  const int b0 = rb_wave_uniform(wave * base_n + (wave < extra ? wave : extra));       // its first block
-
-  const int r = lane & 15, q = lane >> 4;
-  const int lr = lane >> 3, lk = lane & 7;               // line-wide weight loads: 8 rows x 128 B per instruction
+  const NlFwdWave wv(K, row0, row_end);
+  const int r = wv.r, q = wv.q, lr = wv.lr, lk = wv.lk;
   const rb_buf bmu = rb_make_buf(a.mu), bsg = rb_make_buf(a.sigma), bx = rb_make_buf(a.x), bxs = rb_make_buf(a.xs);
-  unsigned wo[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int row = row0 + 8 * i + lr;
-    if (row > row_end - 1) row = row_end - 1;
-    wo[i] = (unsigned)(((int64_t)row * K + 4 * lk) * 4);
-  }
-  float* wtm = &s_wt[wave][0][0];                         // [16 rows][RB_FWD2_WT_LD] of mu
+  float* wtm = &s_wt[wave][0][0];                         // [16 rows][RB_NL_FWD_WT_LD] of mu
   float* wts = &s_wt[wave][1][0];                         // ... of sigma
   unsigned xo[MT], xso[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    int m = m0 + 16 * mt + r;
-    if (m > M - 1) m = M - 1;
-    xo[mt] = (unsigned)((((int64_t)(grp.x_off >> 4) * M + m) * 16 + 4 * q) * 4);
-    xso[mt] = (unsigned)((((int64_t)(grp.ein_off >> 4) * M + m) * 16 + 4 * q) * 4);
-  }
+  wv.x_offsets<MT>(grp.x_off, M, 0, m0, M, xo);
+  wv.x_offsets<MT>(grp.ein_off, M, 0, m0, M, xso);
   const unsigned xstep = (unsigned)M * 64u;               // bytes between consecutive 16-wide k chunks of the activations
-  const int nb_ = row0 + (lane & 15) < row_end ? row0 + (lane & 15) : row_end - 1;
-  const float b_mu = a.bmu[nb_], b_sg = a.bsigma[nb_];
+  const float b_mu = a.bmu[wv.nb], b_sg = a.bsigma[wv.nb];
 
   rb_f32x4 accm[MT], accs[MT];
 #pragma unroll
@@ -149,8 +131,8 @@ __global__ __launch_bounds__(64 * RB_NL_FWD_WAVES) void k_nlr_fwd(NlRowsArgs a) 
     const unsigned so = (unsigned)b * 128u;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      r_mu[d][i] = rb_ld4_buf(bmu, wo[i], so);
-      r_sg[d][i] = rb_ld4_buf(bsg, wo[i], so);
+      r_mu[d][i] = rb_ld4_buf(bmu, wv.wo[i], so);
+      r_sg[d][i] = rb_ld4_buf(bsg, wv.wo[i], so);
     }
   };
   auto load_x = [&](int d, int b) {
@@ -164,22 +146,18 @@ __global__ __launch_bounds__(64 * RB_NL_FWD_WAVES) void k_nlr_fwd(NlRowsArgs a) 
       }
     }
   };
-  // no ring slot is ever loaded with a block past the wave's range (k_nl_fwd3's EXACT form)
-#pragma unroll
-  for (int d = 0; d < RING; ++d)
-    if (d < nsc) { load_w(d, b0 + d); load_x(d, b0 + d); }   // wave-uniform
-  auto compute = [&](int d) {                             // the transpose: what was loaded as 8 rows x 128 B becomes the operand layout
+  auto stage = [&](int d) {                          // the transpose: what was loaded as 8 rows x 128 B becomes the operand layout
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      *reinterpret_cast<float4*>(&wtm[(8 * i + lr) * RB_FWD2_WT_LD + 4 * lk]) = r_mu[d][i];
-      *reinterpret_cast<float4*>(&wts[(8 * i + lr) * RB_FWD2_WT_LD + 4 * lk]) = r_sg[d][i];
+      *reinterpret_cast<float4*>(&wtm[(8 * i + lr) * RB_NL_FWD_WT_LD + 4 * lk]) = r_mu[d][i];
+      *reinterpret_cast<float4*>(&wts[(8 * i + lr) * RB_NL_FWD_WT_LD + 4 * lk]) = r_sg[d][i];
     }
   };
   auto mfmas = [&](int d) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const float4 m4 = *reinterpret_cast<const float4*>(&wtm[r * RB_FWD2_WT_LD + 16 * h + 4 * q]);
-      const float4 s4 = *reinterpret_cast<const float4*>(&wts[r * RB_FWD2_WT_LD + 16 * h + 4 * q]);
+      const float4 m4 = *reinterpret_cast<const float4*>(&wtm[r * RB_NL_FWD_WT_LD + 16 * h + 4 * q]);
+      const float4 s4 = *reinterpret_cast<const float4*>(&wts[r * RB_NL_FWD_WT_LD + 16 * h + 4 * q]);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) { accm[mt] = rb_mfma16(r_x[d][h][mt].x, m4.x, accm[mt]); accs[mt] = rb_mfma16(r_xs[d][h][mt].x, s4.x, accs[mt]); }
 #pragma unroll
@@ -190,13 +168,19 @@ __global__ __launch_bounds__(64 * RB_NL_FWD_WAVES) void k_nlr_fwd(NlRowsArgs a) 
       for (int mt = 0; mt < MT; ++mt) { accm[mt] = rb_mfma16(r_x[d][h][mt].w, m4.w, accm[mt]); accs[mt] = rb_mfma16(r_xs[d][h][mt].w, s4.w, accs[mt]); }
     }
   };
+  // k_nl_fwd3's EXACT ring, written out: no slot is ever loaded with a block past the wave's range.  (As one function template
+  // shared with k_nl_fwd3 the same schedule cost k_nlr_fwd<1> two registers, 168 -> 170, and with them its third wave per SIMD.)
+  const int nsc = wv.nsc, b0 = wv.b0;
+#pragma unroll
+  for (int d = 0; d < RING; ++d)
+    if (d < nsc) { load_w(d, b0 + d); load_x(d, b0 + d); }   // wave-uniform
   const int full = nsc / RING * RING;
   const int steady = full >= RING ? full - RING : 0;      // the LAST full round refills only the slots the tail will consume
   for (int sc0 = 0; sc0 < steady; sc0 += RING) {
 #pragma unroll
     for (int d = 0; d < RING; ++d) {
       const int sc = sc0 + d;
-      compute(d);
+      stage(d);
       load_w(d, b0 + sc + RING);                           // refill the weight half of this ring slot (sc + RING < full <= nsc)
       rb_wave_sync();                                    // the tiles are private to the wave: LDS executes its ops in order
       mfmas(d);
@@ -210,7 +194,7 @@ __global__ __launch_bounds__(64 * RB_NL_FWD_WAVES) void k_nlr_fwd(NlRowsArgs a) 
     for (int d = 0; d < RING; ++d) {
       const int sc = steady + d;
       const bool refill = sc + RING < nsc;               // wave-uniform
-      compute(d);
+      stage(d);
       if (refill) load_w(d, b0 + sc + RING);
       rb_wave_sync();
       mfmas(d);
@@ -222,7 +206,7 @@ __global__ __launch_bounds__(64 * RB_NL_FWD_WAVES) void k_nlr_fwd(NlRowsArgs a) 
 #pragma unroll
   for (int d = 0; d < RING; ++d) {                       // tail: the blocks the last refills brought in, no more loads
     if (full + d < nsc) {                                // wave-uniform
-      compute(d);
+      stage(d);
       rb_wave_sync();
       mfmas(d);
       rb_wave_sync();
@@ -247,7 +231,7 @@ __global__ __launch_bounds__(64 * RB_NL_FWD_WAVES) void k_nlr_fwd(NlRowsArgs a) 
     if (m < M && n < row_end) {
       const float* nz = a.noise_rows + (int64_t)m * a.n_noise;
       const float eo = nz[a.eout_off + n];
-      float o = (vm + eo * vs) + (b_mu + b_sg * eo);      // (n == nb_ for every cell that is stored)
+      float o = (vm + eo * vs) + (b_mu + b_sg * eo);      // (n == wv.nb for every cell that is stored)
       if (a.relu) o = fmaxf(o, 0.0f);
       a.out[(int64_t)m * a.ld_out + n] = o;
       if (a.out_blocked) a.out_blocked[rb_blocked_index(m, n, M)] = o;

@@ -309,7 +309,7 @@ __device__ __forceinline__ float rb_ld1_buf(const rb_buf& b, unsigned lane_off, 
 #endif
 }
 
-// k-blocked activation layout consumed by k_nl_fwd (and written by the epilogues in front of it: conv_fwd.h, noisy_linear.h,
+// k-blocked activation layout consumed by k_nl_fwd (and written by the epilogues in front of it: conv_fwd.h, nl_fwd.h,
 // noisy_rows.h): element (row, k) of a [rows][K] matrix — 16 k of a row are 64 contiguous bytes, the next 16 are rows * 64 further
 __host__ __device__ inline int64_t rb_blocked_index(int row, int k, int rows) {
   return ((int64_t)(k >> 4) * rows + row) * 16 + (k & 15);

@@ -1,6 +1,6 @@
 // replay_update.h — SegmentTree.update on the device: the hashed body for any batch of one workgroup, the one-wave body for a
 // sorted batch, and rb_update_auto, which picks.  Included through replay_internal.h only (it needs ReplayView): the learner
-// runs the priority write-back (agent.py:100) as one workgroup of its own backward launch (noisy_linear.h, fc_gemm.h).
+// runs the priority write-back (agent.py:100) as one workgroup of its own backward launch (nl_bwd.h, fc_gemm.h).
 #pragma once
 
 // ---------------------------------------------------------------------- update --

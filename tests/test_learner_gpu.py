@@ -377,7 +377,7 @@ def test_compat_path_with_foreign_replay(hip):
 
 @pytest.mark.parametrize("base", ["dataeff", "canon"])
 def test_wide_batch_matches_oracle(hip, monkeypatch, base):
-    """Batch 64 (128 online rows): the noisy-linear forward switches to 64-row m-chunks (k_nl_fwd2<0, 4>) and the conv
+    """Batch 64 (128 online rows): the noisy-linear forward switches to 64-row m-chunks (k_nl_fwd3<4>) and the conv
     weight-gradient workgroups sum two images each; loss and every gradient against the oracle on the same inputs."""
     from cabi_adapter import CAbiLearnAdapter, TorchMem
     cfgd = dict(scenarios.LEARN_CONFIGS[base], batch=64, multi_step=3)

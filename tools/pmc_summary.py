@@ -22,7 +22,7 @@ def load(d, counter):
 
 
 def tag_of(name, grid, biggest):
-    """bench.py tag of a kernel instance; the hidden layer's launches are the larger grid of k_nl_fwd2 / k_nl_bwd."""
+    """bench.py tag of a kernel instance; the hidden layer's launches are the larger grid of k_nl_fwd3 / k_nl_bwd."""
     if "k_clip_adam" in name:
         return "clip_adam"
     if "k_fc_gemm_fwd" in name:            # the hidden layer as tiled GEMMs (fc_gemm.h, from 128 rows per net on)
