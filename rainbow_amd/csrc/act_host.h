@@ -4,6 +4,28 @@
 #pragma once
 #include "learner_internal.h"
 
+// Output rows per workgroup of each conv layer on the act path (act_path.h k_act_conv / k_act_fused): at most RB_ACT_MAXPOS
+// positions, and the rows' input patch within RB_ACT_LDS floats.  false = a layer the act path does not cover (no row fits, or a
+// filter beyond RB_ACT_KMAX taps).  rb_debug_launch_plan prints the same numbers (act_path rg=).
+static bool act_conv_rows(const Layout& L, int rg[3]) {
+  rg[0] = rg[1] = rg[2] = 0;
+  for (int layer = 0; layer < L.nconv; ++layer) {
+    const ConvLayer& c = L.conv[layer];
+    int r = RB_ACT_MAXPOS / c.oh;
+    if (r > c.oh) r = c.oh;
+    while (r >= 1 && (int64_t)c.cin * ((r - 1) * c.s + c.ks) * c.ih > RB_ACT_LDS) --r;
+    if (r < 1 || c.K() > RB_ACT_KMAX) return false;
+    rg[layer] = r;
+  }
+  return true;
+}
+// Whether rb_learner_act runs the act path at all (RB_OPTS generic=1 / 2 clears fast_fc); otherwise the training forward
+static bool act_path_covers(const Layout& L, const LearnerCaps& caps, int rg[3]) {
+  rg[0] = rg[1] = rg[2] = 0;
+  if (!caps.fast_fc || (L.F & 3) || (L.H & 3)) return false;
+  return act_conv_rows(L, rg);
+}
+
 // One state through the act path (act_path.h).  RB_ERR_STATE (without touching the error string) = geometry not
 // covered, the caller falls back to the training kernels.
 // Returns RB_OK (logits ready: the caller launches the head), 1 (the one-launch path ran the head as well and wrote
@@ -11,16 +33,8 @@
 static int act_forward_single(rb_learner* l, const float* state_dev, const NetPtrs& on, int noisy, hipStream_t stream,
                               int32_t* head_action_out, float* head_q_out) {
   const Layout& L = l->L;
-  if (!l->caps.fast_fc || (L.F & 3) || (L.H & 3)) return RB_ERR_STATE;   // RB_OPTS generic=1 / 2 also lands here
   int rg[3];
-  for (int layer = 0; layer < L.nconv; ++layer) {   // output rows per workgroup: <= 128 positions, patch fits the LDS
-    const ConvLayer& c = L.conv[layer];
-    int r = RB_ACT_MAXPOS / c.oh;
-    if (r > c.oh) r = c.oh;
-    while (r >= 1 && (int64_t)c.cin * ((r - 1) * c.s + c.ks) * c.ih > RB_ACT_LDS) --r;
-    if (r < 1 || c.K() > RB_ACT_KMAX) return RB_ERR_STATE;
-    rg[layer] = r;
-  }
+  if (!act_path_covers(L, l->caps, rg)) return RB_ERR_STATE;            // RB_OPTS generic=1 / 2 also lands here
   ActFusedArgs f;
   memset(&f, 0, sizeof(f));
   const float* x = state_dev;

@@ -1,5 +1,5 @@
 // launch_plan_debug.h — rb_debug_launch_plan: the plans of learner_plan.h as text, one line per launch of a learn step, in launch
-// order (the sequence of learn_impl), then the forward lines of a one-row f32 forward.  Stateless: no handle, no device.
+// order (the sequence of learn_impl), then the forward lines of a one-row f32 forward and the act path's row groups.  Stateless: no handle, no device.
 // Included by learner.hip only.
 #pragma once
 #include "learner_plan.h"
@@ -73,9 +73,9 @@ extern "C" int rb_debug_launch_plan(const rb_learner_config_t* cfg, const char* 
            b.z_threads, b.zg.dw_x, b.zg.dw_y, b.zg.dx_x, b.zg.dx_y, b.zg.dx_z, b.pipe ? 1 : 0, b.z_ct, b.z_tall ? 1 : 0);
     if (b.pack) t.line("pack_factors kernel=k_pack_factors grid=16x5x1 block=256");
     t.line("fc_h_bwd kernel=%s grid=%ux1x1 block=%u dw=%dx%d dx=%dx%dx%d writeback=%d h_ct=%d gemm_bwd=%d fuse_norm=%d defer_dw=%d "
-           "implicit_sigma=%d hsplits=%d norm_slots=%d lazy_dfeat=%d", fc_bwd_kernel_name[b.h_kernel], b.h_blocks, b.h_threads, b.hg.dw_x, b.hg.dw_y,
+           "implicit_sigma=%d hsplits=%d rows_per_split=%d norm_slots=%d lazy_dfeat=%d", fc_bwd_kernel_name[b.h_kernel], b.h_blocks, b.h_threads, b.hg.dw_x, b.hg.dw_y,
            b.hg.dx_x, b.hg.dx_y, b.hg.dx_z, b.up_enabled ? 1 : 0, b.h_ct, b.gemm_bwd ? 1 : 0, b.fuse_norm ? 1 : 0, b.defer_dw ? 1 : 0,
-           b.implicit_sigma ? 1 : 0, b.hsplits, b.norm_slots, b.lazy_dfeat ? 1 : 0);
+           b.implicit_sigma ? 1 : 0, b.hsplits, b.rows_per_split, b.norm_slots, b.lazy_dfeat ? 1 : 0);
     if (!b.lazy_dfeat) t.line("dfeat_finish kernel=k_dfeat_finish splits=%d", b.hsplits);
   }
   auto dx_line = [&](int layer) {
@@ -104,6 +104,12 @@ extern "C" int rb_debug_launch_plan(const rb_learner_config_t* cfg, const char* 
   t.line("reduce_conv_dw kernel=k_reduce_conv_dw_all grid=%ux1x1 block=64 snapshot=%d", plan_conv_reduce_blocks(L, b.implicit_sigma),
          b.implicit_sigma ? 1 : 0);
   plan_text_forward(t, in, "act_", 1, 0, true);
+  {
+    // rb_learner_act's own path (act_host.h): covered=0 is the training forward above; rg = output rows per workgroup and layer
+    int rg[3];
+    const bool covered = act_path_covers(L, caps, rg);
+    t.line("act_path covered=%d rg=%d/%d/%d", covered ? 1 : 0, rg[0], rg[1], rg[2]);
+  }
   if (t.full) {
     rb_set_error("rb_debug_launch_plan: %lld bytes are too few for the plan", (long long)cap);
     return RB_ERR_INVALID;

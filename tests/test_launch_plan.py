@@ -301,3 +301,92 @@ def test_bad_arguments_are_refused_with_a_message(emu):
     buf = C.create_string_buffer(1 << 14)
     assert emu.rb_debug_launch_plan(C.byref(cfg), b"no_such_key=1", 256, 0, 1, 0, buf, 1 << 14) < 0
     assert b"no_such_key" in emu.rb_last_error()
+
+
+# ------------------------------------------------------------- the history / hidden table (tests/shape_range_scenarios.py)
+def shape_range_plan(lib, case, flags=0):
+    import shape_range_scenarios as SR
+    c = SR.case_config(case)
+    return plan(lib, batch=c["batch"], atoms=c["atoms"], actions=c["actions"], history=c["history"], hidden=c["hidden"],
+                architecture=0 if c["architecture"] == "canonical" else 1, flags=flags, cap=1 << 15)
+
+
+# row: the plan fields the row's "crosses" column claims — tag.field: value; a tag alone with None: that line is absent
+SHAPE_RANGE_PINS = {
+    # history < 4: off the whole-K first-layer kernel (canonical), the same split-K kernel part filled (data-efficient)
+    "c-hist1": {"caps.fast_conv": 1, "conv1_fwd.kernel": "k_conv_fwd_lds<GeomC1>", "conv_dw_all.kernel": "k_conv_dw_all<3>", "act_path.rg": (6, 9, 7)},
+    "c-hist2": {"caps.fast_conv": 1, "conv1_fwd.kernel": "k_conv_fwd_lds<GeomC1>", "conv_dw_all.kernel": "k_conv_dw_all<3>", "act_path.rg": (6, 9, 7)},
+    "d-hist1": {"caps.fast_conv": 1, "conv1_fwd.kernel": "k_conv_fwd_lds<GeomD1>", "conv_dw_all.kernel": "k_conv_dw_all<2>", "act_path.rg": (8, 3, 0)},
+    "d-hist3": {"caps.fast_conv": 1, "conv1_fwd.kernel": "k_conv_fwd_lds<GeomD1>", "conv_dw_all.kernel": "k_conv_dw_all<2>", "act_path.rg": (8, 3, 0)},
+    # history > 4: every conv on k_gemm behind the streamed FC, and the act path's patch limit
+    "c-hist8": {"caps.fast_conv": 0, "caps.fast_fc": 1, "conv1_fwd.kernel": "k_gemm<ConvFwdProb<GeomC1>>", "fc_h_fwd.kernel": "k_nl_fwd3<2>",
+                "feat_block_copy.kernel": "k_block_copy", "dfeat_finish.splits": 1, "fc_h_bwd.lazy_dfeat": 0, "conv_dw_all": None,
+                "act_path.covered": 1, "act_path.rg": (4, 9, 7)},
+    "c-hist16": {"caps.fast_conv": 0, "caps.fast_fc": 1, "conv1_fwd.kernel": "k_gemm<ConvFwdProb<GeomC1>>", "fc_h_fwd.kernel": "k_nl_fwd3<2>",
+                 "feat_block_copy.kernel": "k_block_copy", "dfeat_finish.splits": 1, "fc_h_bwd.lazy_dfeat": 0, "conv_dw_all": None,
+                 "act_path.covered": 1, "act_path.rg": (1, 9, 7)},
+    "d-hist16": {"caps.fast_conv": 0, "caps.fast_fc": 1, "conv1_fwd.kernel": "k_gemm<ConvFwdProb<GeomD1>>", "fc_h_fwd.kernel": "k_nl_fwd3<2>",
+                 "feat_block_copy.kernel": "k_block_copy", "dfeat_finish.splits": 1, "fc_h_bwd.lazy_dfeat": 0, "conv_dw_all": None,
+                 "act_path.covered": 1, "act_path.rg": (2, 3, 0)},
+    # hidden 1 / 3: generic FC, and rb_learner_act on the training forward
+    "d-h1": {"caps.fast_fc": 0, "caps.fast_conv": 1, "fc_h_fwd.kernel": "k_gemm", "fc_h_dx.kernel": "k_gemm<FcHDxProb>", "fc_h_bwd": None,
+             "act_path.covered": 0},
+    "d-h3": {"caps.fast_fc": 0, "caps.fast_conv": 1, "fc_h_fwd.kernel": "k_gemm", "fc_h_dx.kernel": "k_gemm<FcHDxProb>", "fc_h_bwd": None,
+             "act_path.covered": 0},
+    # row splits of the hidden layer's input gradient, summed by the last conv layer's backward kernels (lazy_dfeat)
+    "d-h128": {"caps.fast_fc": 1, "caps.xs": 1, "fc_h_bwd.hsplits": 1, "fc_h_bwd.rows_per_split": 256, "fc_h_bwd.lazy_dfeat": 1},
+    "d-h160": {"caps.fast_fc": 1, "caps.xs": 2, "fc_h_bwd.hsplits": 2, "fc_h_bwd.rows_per_split": 160, "fc_h_bwd.lazy_dfeat": 1},
+    "d-h288": {"caps.fast_fc": 1, "caps.xs": 3, "fc_h_bwd.hsplits": 3, "fc_h_bwd.rows_per_split": 192, "fc_h_bwd.lazy_dfeat": 1},
+    "d-h352": {"caps.fast_fc": 1, "caps.xs": 3, "fc_h_bwd.hsplits": 3, "fc_h_bwd.rows_per_split": 240, "fc_h_bwd.lazy_dfeat": 1},    # 240 / 240 / 224
+    # both sides of the fast_fc limit, and the accepted maximum
+    "d-h4096": {"caps.fast_fc": 1, "caps.xs": 4, "fc_h_fwd.kernel": "k_nl_fwd3<2>", "fc_z_fwd.kernel": "k_nl_fwd3<2>", "fc_h_bwd.kernel": "k_nl_bwd<false>",
+                "fc_h_bwd.hsplits": 4, "fc_h_bwd.fuse_norm": 1, "act_path.covered": 1},
+    "d-h4128": {"caps.fast_fc": 0, "caps.xs": 52, "fc_h_fwd.kernel": "k_gemm", "fc_z_fwd.kernel": "k_gemm", "fc_h_dx.kernel": "k_gemm<FcHDxProb>",
+                "dfeat_finish.splits": 52, "fc_h_bwd": None, "act_path.covered": 0},
+    "d-h8192": {"caps.fast_fc": 0, "caps.xs": 54, "fc_h_fwd.kernel": "k_gemm", "fc_z_fwd.kernel": "k_gemm", "fc_h_dx.kernel": "k_gemm<FcHDxProb>",
+                "dfeat_finish.splits": 54, "fc_h_bwd": None, "act_path.covered": 0},
+    # the fused norm's 16 384 sum-of-squares slots at batch 33
+    "c-b33-h2176": {"caps.fast_fc": 1, "fc_h_fwd.kernel": "k_nl_fwd3<2>", "fc_h_bwd.kernel": "k_nl_bwd<false>", "fc_h_bwd.fuse_norm": 1,
+                    "fc_h_bwd.norm_slots": 16227, "fc_h_bwd.implicit_sigma": 0, "fc_h_bwd.hsplits": 4},
+    "c-b33-h2208": {"caps.fast_fc": 1, "fc_h_fwd.kernel": "k_nl_fwd3<2>", "fc_h_bwd.kernel": "k_nl_bwd<false>", "fc_h_bwd.fuse_norm": 0,
+                    "fc_h_bwd.norm_slots": 0, "fc_h_bwd.implicit_sigma": 0, "fc_h_bwd.hsplits": 4},
+    # the tiled forward GEMM beyond the tile count that lets it split K
+    "d-b1024-h4096": {"caps.fast_fc": 1, "conv1_fwd.kernel": "k_conv_fwd_full<GeomD1>", "fc_h_fwd.kernel": "k_fc_gemm_fwd", "fc_h_fwd.tiles": 1536,
+                      "fc_h_fwd.S": 1, "fc_h_bwd.kernel": "k_fc_gemm_bwd", "fc_h_bwd.fuse_norm": 1, "fc_h_bwd.hsplits": 4},
+}
+
+
+def test_every_row_of_the_history_and_hidden_table_is_pinned():
+    import shape_range_scenarios as SR
+    assert set(SHAPE_RANGE_PINS) == set(SR.CASES)
+
+
+@pytest.mark.parametrize("case", sorted(SHAPE_RANGE_PINS))
+def test_history_and_hidden_table_reaches_what_each_row_claims(emu, case):
+    p = shape_range_plan(emu, case)
+    for key, want in SHAPE_RANGE_PINS[case].items():
+        tag, _, field = key.partition(".")
+        if want is None:
+            assert tag not in p, (case, tag, p[tag])
+        else:
+            assert tag in p and p[tag][field] == want, (case, key, p.get(tag), want)
+
+
+@pytest.mark.parametrize("case", ["c-b33-h2176", "c-b33-h2208"])
+def test_implicit_sigma_is_not_taken_at_batch_33(emu, case):
+    """Neither the pipelined weight-gradient body (batch <= 32) nor the tiled GEMM (batch >= 128): the flag Agent sets changes
+    nothing on either side of the fused norm's slot limit, and the noise snapshot behind the conv reduction is not taken."""
+    p, q = shape_range_plan(emu, case), shape_range_plan(emu, case, flags=_lib.LEARNER_IMPLICIT_SIGMA)
+    assert q["fc_h_bwd"]["implicit_sigma"] == 0 and q["reduce_conv_dw"]["snapshot"] == 0
+    assert p == q
+
+
+def test_act_path_rows_per_workgroup_follow_the_patch_limit(emu):
+    """act_host.h act_conv_rows: at most 128 positions, and the rows' input patch within RB_ACT_LDS = 15 360 floats — canonical
+    conv1 at history h stages h * ((rg - 1) * 4 + 8) * 84 floats."""
+    want = {1: 6, 4: 6, 6: 6, 7: 5, 8: 4, 9: 4, 10: 3, 11: 3, 12: 2, 15: 2, 16: 1}
+    for hist, rg in want.items():
+        p = plan(emu, batch=4, history=hist, hidden=64)["act_path"]
+        assert p["covered"] == 1 and p["rg"] == (rg, 9, 7), (hist, p)
+        assert hist * ((rg - 1) * 4 + 8) * 84 <= 15360 and (rg == 6 or hist * (rg * 4 + 8) * 84 > 15360)
+    assert plan(emu, opts="generic=2")["act_path"]["covered"] == 0

@@ -2,7 +2,10 @@
 For each case: the first seed in [0, N) for which the ORACLE ALONE reports a hidden_relu_margin of at least RELU_MARGIN in both of the
 test's steps (step 1 runs on the oracle's own post-Adam parameters of step 0), or 'none': the case then hands the device's ReLU
 decisions to the oracle (masked).  --best: all N seeds, and the one whose smaller margin is largest (a seed well clear of the bound
-where the first one only just passes).  Prints the margins it saw and the oracle's time for the two steps."""
+where the first one only just passes).  Prints the margins it saw and the oracle's time for the two steps.
+usage: python tools/ladder_seeds.py --shape-range [case ...] [--seeds N] — the same for tests/shape_range_scenarios.py's table: the first
+seed in [0, N) (default 14) that gives both steps a margin of at least 2.5 x RELU_MARGIN and the act calls their top-two gap; prints the
+row's seed and margins as the table holds them, and 'none' where the row has to be masked."""
 import os
 import sys
 import time
@@ -27,6 +30,25 @@ def margin(run, k):
 
 
 args = sys.argv[1:]
+if "--shape-range" in args:
+    import shape_range_scenarios as SR  # noqa: E402
+    args.remove("--shape-range")
+    n = 14
+    if "--seeds" in args:
+        i = args.index("--seeds")
+        n = int(args[i + 1])
+        del args[i:i + 2]
+    for case in args or list(SR.CASES):
+        t0 = time.time()
+        found, masked, seen = SR.find_seed(case, n)
+        tried = "; ".join("%d: %.1e %.1e gap %.1e" % (s, m[0], m[1], g) for s, m, g in seen)
+        if found:
+            print("%-14s seed %d   margins (%.1e, %.1e)   act gap %.3e   (%.1f s)   seen: %s" % (case, found[0], found[1][0], found[1][1], found[2],
+                                                                                             time.time() - t0, tried), flush=True)
+        else:
+            print("%-14s seed none: masked, on seed %s (the first whose act calls have their gap)   (%.1f s)   seen: %s"
+                  % (case, masked[0] if masked else "none", time.time() - t0, tried), flush=True)
+    sys.exit(0)
 n = 12
 best = "--best" in args
 if best:
