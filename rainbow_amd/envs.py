@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .agent import current_stream_handle
+from ._util import current_stream_handle
 
 
 class _DeviceEnv:
@@ -26,6 +26,7 @@ class _DeviceEnv:
     one stream.  A game supplies _PREFIX (its rb_* entry points), _create() and _step_call()."""
     ACTIONS = 3
     _PREFIX = None
+    _h = None                  # (close() is safe on an object whose construction failed early)
 
     def __init__(self, streams, device, seed, history_length):
         self.device = torch.device(device)
@@ -50,7 +51,7 @@ class _DeviceEnv:
         return getattr(self._lib, "%s_%s" % (self._PREFIX, name))
 
     def close(self):
-        if getattr(self, "_h", None):
+        if self._h:
             self._fn("destroy")(self._h)
             self._h = None
 

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .agent import current_stream_handle
+from ._util import current_stream_handle
 
 
 def stream_quotas(streams, episodes):
@@ -22,6 +22,8 @@ def stream_quotas(streams, episodes):
 
 
 class EpisodeTally:
+    _h = None                  # (close() is safe on an object whose construction failed early)
+
     def __init__(self, streams, episodes, device):
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -33,7 +35,7 @@ class EpisodeTally:
             L.check(self._lib, self._lib.rb_tally_create(C.byref(self._h), self.streams, self.episodes))
 
     def close(self):
-        if getattr(self, "_h", None):
+        if self._h:
             self._lib.rb_tally_destroy(self._h)
             self._h = None
 

@@ -20,6 +20,9 @@ Random-shift augmentation (DrQ): `args.augment_pad = p` (1..8; absent or 0 = off
 stack by (dy, dx) in [-p, p] with edge replication — `states` and `next_states` independently, all `history` frames of one stack
 alike — inside the frame-stack gather (rb_replay_gather_shifted).  Only `sample_device(gather=True)` and `sample()` are shifted;
 `__next__`, `state_at` / `states_at` (validation, evaluation) never are.
+
+This module: construction, sampling and priorities.  The write side (append and its per-stream forms) is memory_append.py; the
+column table, save_to / load_from and pickling are memory_state.py.
 """
 import ctypes as C
 import os
@@ -28,6 +31,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._util import current_stream_handle
+from .memory_append import ReplayAppend
+from .memory_state import ReplayState
 
 
 class _TransitionsView:
@@ -64,7 +70,7 @@ class _TransitionsView:
         return float(self._hdr().total)
 
 
-class ReplayMemory:
+class ReplayMemory(ReplayAppend, ReplayState):
     # The reference redraws until the batch is valid (memory.py:128-132).  The device loop is bounded, but generously: a
     # redraw costs ~4 us inside the one sampler launch, and hitting the bound means no valid batch exists at all (buffer
     # too small for the batch).  Then the batch gets zero importance weights (a zero-gradient step) and
@@ -77,8 +83,7 @@ class ReplayMemory:
     # write-back first.  Operands are copied at the call — numpy arrays (the reference's call site, agent.py:100) by their
     # upload, device tensors into a two-slot staging buffer this object owns (_stage_operands) — so the caller may reuse its
     # loss / index tensors at once, as with the reference's immediate update.
-    _pending = None
-    _stage = None
+    _pending = None             # (these two: so that __del__ and `_h` are safe on an object whose construction failed early)
     _handle = None
     streams = 1                 # (a pickle written before interleaved streams existed restores as one stream)
     augment_pad = 0             # (a pickle written before the random-shift option existed restores with it off)
@@ -108,7 +113,6 @@ class ReplayMemory:
         if self.device.type != "cuda":
             raise RuntimeError("rainbow_amd.ReplayMemory lives in HBM: args.device must be a cuda (ROCm) device, got %s"
                                % self.device)
-        self._lib = L.load()
         self.capacity = int(capacity)
         self.history = int(args.history_length)
         self.discount = float(args.discount)
@@ -122,14 +126,34 @@ class ReplayMemory:
         self.augment_pad = self._checked_pad(getattr(args, "augment_pad", 0))
         self._aug_draw = 0
         self._lazy = os.environ.get("RAINBOW_AMD_LAZY_PRIORITIES", "1") != "0"
+        self._init_runtime()
+        self.current_idx = 0
+
+    def _init_runtime(self):
+        """Everything outside the saved state, built by __init__ and again by __setstate__: the library and replay handles, the
+        pending write-back and its staging ring, the output buffers and their pointer cache, and `_keep`, which holds every
+        operand a launch in flight still reads (injected uniforms and shifts, applied write-backs, the last device round).
+        __getstate__ leaves out ReplayState._RUNTIME; `_ptr_cache` alone is pickled as it always was and rebuilt here."""
+        self._lib = L.load()
         self._pending = None
         self._stage = {}
-        self._create()
-        self.transitions = _TransitionsView(self)
+        self._keep = {}
         self._out = {}
         self._ptr_cache = {}
-        self.current_idx = 0
+        self._bufs = None                                       # frame_source(): the column pointers, asked once
+        self._create()
+        self.transitions = _TransitionsView(self)
         self._init_beta_source()
+
+    def begin_external_draw(self, batch):
+        """For a caller that issues the draw itself (rb_learner_train_step): what sample_device() does before its launch — a
+        pending write-back applied, -beta in HBM brought up to date — and the output buffers of `batch`."""
+        if self._pending is not None:
+            self.flush()
+        if float(self.priority_weight) != self._neg_beta_val:
+            self._sync_beta()
+        o = self._out.get(batch)
+        return o if o is not None else self._buffers(batch)
 
     @classmethod
     def _checked_pad(cls, pad):
@@ -164,17 +188,14 @@ class ReplayMemory:
     def __del__(self):
         try:
             self._pending = None
-            if getattr(self, "_handle", None):
+            if self._handle:
                 self._lib.rb_replay_destroy(self._handle)
                 self._handle = None
         except Exception:
             pass
 
     def _stream(self):
-        raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)      # one C call instead of a Stream object (~4 us) per launch
-        if raw is not None:
-            return raw(self.device.index if self.device.index is not None else torch.cuda.current_device())
-        return torch.cuda.current_stream(self.device).cuda_stream
+        return current_stream_handle(self.device)
 
     def _header(self):
         hdr = L.ReplayHeader()
@@ -197,133 +218,13 @@ class ReplayMemory:
         return self._out[key]
 
     # ------------------------------------------------------------------ reference API
-    def append(self, state, action, reward, terminal):
-        """memory.py:105-108.  `state` float32 [h,84,84] in [0,1] on the device (env.py:52,77)."""
-        self._one_stream("append")
-        if self._stream_t_dev is not None:      # device rounds came before: fetch the episode timestep they left
-            self.stream_t
-        st = state
-        if st.dtype != torch.float32 or st.device != self.device or not st.is_contiguous():     # (env.py hands over exactly this)
-            st = state.to(device=self.device, dtype=torch.float32).contiguous()
-        rc = self._lib.rb_replay_append(self._h, st.data_ptr(), int(self.t), int(action), float(reward),
-                                        0 if terminal else 1, self._stream())
-        if rc != 0:
-            L.check(self._lib, rc)
-        self.t = 0 if terminal else self.t + 1
-        self.stream_t[0] = self.t
-
-    def _one_stream(self, what):
-        if self.streams != 1:
-            raise RuntimeError("ReplayMemory.%s: this memory interleaves %d environment streams; append whole rounds with "
-                               "append_streams(states, actions, rewards, terminals)" % (what, self.streams))
-
-    def append_streams(self, states, actions, rewards, terminals=None, nonterminals=None):
-        """One round of memory.py:105-108 for every environment stream at once (one launch): `states` float32 [S,h,84,84] on
-        the device (the batch Agent.act_batch just acted on), actions / rewards / terminals length-S sequences.  Stream s
-        keeps its own episode timestep (stream_t[s]).  The same ring, tree and header as S appends in stream order.
-        When actions, rewards and terminals are all torch tensors on this memory's device (Agent.act_batch(device_out=True),
-        a rainbow_amd.envs environment) the round stays on the device: nothing is read back and nothing synchronises; the
-        per-stream timesteps then live in a device vector (`stream_t` reads it back on demand).  On that path `terminals`
-        (bool / uint8) is inverted on the device, or pass `nonterminals=` (uint8 device tensor, 1 = the episode goes on: what
-        a rainbow_amd.envs environment keeps as `env.nonterminals`) instead and save that launch.  Host and device rounds
-        may be mixed freely and give the same replay bit for bit."""
-        S = self.streams
-        st = states
-        if st.dtype != torch.float32 or st.device != self.device or not st.is_contiguous():
-            st = states.to(device=self.device, dtype=torch.float32).contiguous()
-        if tuple(st.shape) != (S, self.history, 84, 84):
-            raise ValueError("append_streams: states must be [%d, %d, 84, 84], got %s" % (S, self.history, tuple(st.shape)))
-        flags = nonterminals if nonterminals is not None else terminals
-        if flags is None:
-            raise ValueError("append_streams: give terminals or nonterminals")
-        if all(torch.is_tensor(x) and x.is_cuda and (self.device.index is None or x.device.index == self.device.index)
-               for x in (actions, rewards, flags)):
-            return self._append_streams_device(st, actions, rewards, terminals, nonterminals)
-        if nonterminals is not None:
-            terminals = ~np.asarray(nonterminals.cpu() if torch.is_tensor(nonterminals) else nonterminals, dtype=bool)
-        terminals = np.asarray(terminals.cpu() if torch.is_tensor(terminals) else terminals, dtype=bool).reshape(-1)
-        ac = np.ascontiguousarray(np.asarray(actions.cpu() if torch.is_tensor(actions) else actions, dtype=np.int32).reshape(-1))
-        rw = np.ascontiguousarray(np.asarray(rewards.cpu() if torch.is_tensor(rewards) else rewards, dtype=np.float32).reshape(-1))
-        if len(terminals) != S or len(ac) != S or len(rw) != S:
-            raise ValueError("append_streams: actions, rewards and terminals need %d entries each" % S)
-        ts = self.stream_t              # (reads the device vector back first when device rounds came before)
-        nt = (~terminals).astype(np.uint8)
-        L.check(self._lib, self._lib.rb_replay_append_streams(self._h, st.data_ptr(), ts.ctypes.data, ac.ctypes.data, rw.ctypes.data,
-                                                              nt.ctypes.data, self._stream()))
-        self.stream_t = np.where(terminals, 0, ts + 1).astype(np.int32)       # memory.py:108, per stream
-        if S == 1:
-            self.t = int(self.stream_t[0])
-
-    def _append_streams_device(self, st, actions, rewards, terminals, nonterminals):
-        S = self.streams
-        if actions.numel() != S or rewards.numel() != S or (nonterminals if nonterminals is not None else terminals).numel() != S:
-            raise ValueError("append_streams: actions, rewards and terminals need %d entries each" % S)
-        ac = actions if actions.dtype == torch.int32 and actions.is_contiguous() else actions.to(torch.int32).contiguous()
-        rw = rewards if rewards.dtype == torch.float32 and rewards.is_contiguous() else rewards.to(torch.float32).contiguous()
-        if nonterminals is not None:
-            nt = nonterminals if nonterminals.dtype == torch.uint8 and nonterminals.is_contiguous() else (nonterminals != 0).contiguous()
-        else:
-            nt = (terminals == 0).contiguous()                  # nonterminal = 1 - terminal on the device (a bool tensor is one 0 / 1 byte each)
-        if self._stream_t_dev is None:                          # host rounds (or none) came before: continue from their counters
-            if not np.any(self._stream_t_host):                 # (a fresh memory: a fill, no synchronising upload)
-                self._stream_t_dev = torch.zeros(S, dtype=torch.int32, device=self.device)
-            else:
-                self._stream_t_dev = torch.from_numpy(np.ascontiguousarray(self._stream_t_host, dtype=np.int32)).to(self.device)
-        self._dev_round = (st, ac, rw, nt)                      # operands stay alive until the next round replaces them
-        rc = self._lib.rb_replay_append_streams_dev(self._h, st.data_ptr(), self._stream_t_dev.data_ptr(), ac.data_ptr(),
-                                                    rw.data_ptr(), nt.data_ptr(), self._stream())
-        if rc != 0:
-            L.check(self._lib, rc)
-
-    # the per-stream episode timesteps: a host array while rounds come with host operands, a device vector (updated by the
-    # append kernel) while they come with device operands.  Reading `stream_t` is always truthful: it fetches the device
-    # vector (one small synchronising copy) and hands the counters back to the host side; save_to and pickling go through it.
-    _stream_t_dev = None
-    _dev_round = None
-
-    @property
-    def stream_t(self):
-        if self._stream_t_dev is not None:
-            self._stream_t_host = self._stream_t_dev.cpu().numpy().astype(np.int32)
-            self._stream_t_dev = None
-            if self.streams == 1:
-                self.t = int(self._stream_t_host[0])
-        return self._stream_t_host
-
-    @stream_t.setter
-    def stream_t(self, value):
-        self._stream_t_host = value
-        self._stream_t_dev = None
-
-    def append_batch(self, frames_u8, actions, rewards, terminals):
-        """n sequential appends of already-quantised last frames (uint8 [n,84,84], device)."""
-        self._one_stream("append_batch")
-        if self._stream_t_dev is not None:
-            self.stream_t
-        n = int(frames_u8.shape[0])
-        terminals = np.asarray(terminals, dtype=bool)
-        ts = np.empty(n, dtype=np.int32)
-        t = self.t
-        for i in range(n):
-            ts[i] = t
-            t = 0 if terminals[i] else t + 1
-        self.t = t
-        self.stream_t[0] = t
-        d = self.device
-        fr = frames_u8.to(device=d, dtype=torch.uint8).contiguous()
-        ts_d = torch.from_numpy(ts).to(d)
-        ac_d = torch.as_tensor(np.asarray(actions, dtype=np.int32)).to(d)
-        rw_d = torch.as_tensor(np.asarray(rewards, dtype=np.float32)).to(d)
-        nt_d = torch.from_numpy((~terminals).astype(np.uint8)).to(d)
-        L.check(self._lib, self._lib.rb_replay_append_batch(self._h, fr.data_ptr(), ts_d.data_ptr(), ac_d.data_ptr(),
-                                                            rw_d.data_ptr(), nt_d.data_ptr(), n, self._stream()))
-        torch.cuda.current_stream(d).synchronize()   # the temporaries above must outlive the kernels
-
     def failed_samples(self):
         """Sampler launches completed so far that found no valid batch within MAX_ATTEMPTS (read from pinned host memory
         the kernel writes: no synchronisation)."""
         n = C.c_int64(0)
-        L.check(self._lib, self._lib.rb_replay_failed_samples(self._handle, C.byref(n)))
+        rc = self._lib.rb_replay_failed_samples(self._handle, C.byref(n))      # (asked on every learn step)
+        if rc != 0:
+            L.check(self._lib, rc)
         return int(n.value)
 
     def dropped_updates(self):
@@ -347,9 +248,10 @@ class ReplayMemory:
 
     def frame_source(self):
         """(frames_ptr, windows_ptr, window_len): lets the learner read frames straight from the ring (zero-copy)."""
-        if not hasattr(self, "_bufs"):
-            self._bufs = L.ReplayBuffers()
-            L.check(self._lib, self._lib.rb_replay_buffers(self._h, C.byref(self._bufs)))
+        if self._bufs is None:
+            b = L.ReplayBuffers()
+            L.check(self._lib, self._lib.rb_replay_buffers(self._h, C.byref(b)))
+            self._bufs = b
         return self._bufs.frames_dev, self._bufs.window_dev, int(self._bufs.window_len)
 
     def sample_device(self, batch_size, unit_uniforms=None, gather=True, noise_job=None, stream=None, shifts=None):
@@ -369,8 +271,8 @@ class ReplayMemory:
             self._sync_beta()
         uu_ptr, attempts = None, self.MAX_ATTEMPTS
         if unit_uniforms is not None:
-            self._uu = unit_uniforms.to(device=self.device, dtype=torch.float64).contiguous()
-            uu_ptr, attempts = self._uu.data_ptr(), int(self._uu.shape[0])
+            uu = self._keep["uu"] = unit_uniforms.to(device=self.device, dtype=torch.float64).contiguous()
+            uu_ptr, attempts = uu.data_ptr(), int(uu.shape[0])
         # the output buffers are persistent: their addresses are looked up once per (batch, gather), not per call (the
         # host side of a learn step is about as long as its GPU side at batch 32 — every microsecond here is on the clock)
         key = (int(batch_size), bool(gather))
@@ -392,7 +294,7 @@ class ReplayMemory:
             self._pending = None
             rc = self._lib.rb_replay_update_sample(self._handle, pend[0].data_ptr(), pend[1].data_ptr(), int(pend[0].numel()), key[0],
                                                    float(self.priority_weight), uu_ptr, attempts, *ptrs, stream)
-            self._applied = pend      # (its operands stay alive until the launch after this one)
+            self._keep["applied"] = pend      # (its operands stay alive until the launch after this one)
         else:
             rc = self._lib.rb_replay_sample(self._handle, key[0], float(self.priority_weight), uu_ptr, attempts, *ptrs, stream)
         if rc != 0:
@@ -411,10 +313,10 @@ class ReplayMemory:
             sh = o["shifts"] = torch.zeros(B, 2, 2, dtype=torch.int8, device=self.device)
         in_ptr = None
         if shifts is not None:
-            self._shifts_in = torch.as_tensor(shifts).to(device=self.device, dtype=torch.int8).contiguous()
-            if tuple(self._shifts_in.shape) != (B, 2, 2):
-                raise ValueError("sample_device: shifts must be [%d, 2, 2], got %s" % (B, tuple(self._shifts_in.shape)))
-            in_ptr = self._shifts_in.data_ptr()
+            sh_in = self._keep["shifts_in"] = torch.as_tensor(shifts).to(device=self.device, dtype=torch.int8).contiguous()
+            if tuple(sh_in.shape) != (B, 2, 2):
+                raise ValueError("sample_device: shifts must be [%d, 2, 2], got %s" % (B, tuple(sh_in.shape)))
+            in_ptr = sh_in.data_ptr()
         rc = self._lib.rb_replay_gather_shifted(self._handle, B, int(self.augment_pad), int(self._aug_draw), in_ptr,
                                                 o["states"].data_ptr(), o["next_states"].data_ptr(), sh.data_ptr(), stream)
         if rc != 0:
@@ -459,12 +361,6 @@ class ReplayMemory:
             priorities = slot[1]
         return idxs, priorities
 
-    def _is_own_index_buffer(self, t):
-        for o in self._out.values():
-            if o["tree_idxs"] is t:
-                return True
-        return False
-
     def update_priorities(self, idxs, priorities, _immediate=False, donate=False):
         """memory.py:157-159.  Accepts numpy arrays (reference call site agent.py:100) or device tensors.  By default the
         write-back is recorded and rides in the next sample_device() launch (RAINBOW_AMD_LAZY_PRIORITIES); caller-owned device
@@ -486,16 +382,15 @@ class ReplayMemory:
             p_d = priorities.to(device=d, dtype=torch.float32).contiguous()
             # (the index buffer sample_device() hands out is this object's: the launch that applies the write-back reads it
             # before its sampler part refills it)
-            stage_i = not own_i and not donate and not self._is_own_index_buffer(idxs)
+            stage_i = not own_i and not donate and not any(o["tree_idxs"] is idxs for o in self._out.values())
             stage_p = not own_p and not donate
             if stage_i or stage_p:          # an operand is still the caller's own device tensor
                 i_d, p_d = self._stage_operands(i_d, p_d, stage_i, stage_p)
-            self._upd = self._pending = (i_d, p_d)
+            self._keep["upd"] = self._pending = (i_d, p_d)
             return
-        self._upd = (idxs.to(device=d, dtype=torch.int64).contiguous(),
-                     priorities.to(device=d, dtype=torch.float32).contiguous())
-        L.check(self._lib, self._lib.rb_replay_update_priorities(self._handle, self._upd[0].data_ptr(),
-                                                                 self._upd[1].data_ptr(), int(self._upd[0].numel()),
+        i_d, p_d = self._keep["upd"] = (idxs.to(device=d, dtype=torch.int64).contiguous(),
+                                        priorities.to(device=d, dtype=torch.float32).contiguous())
+        L.check(self._lib, self._lib.rb_replay_update_priorities(self._handle, i_d.data_ptr(), p_d.data_ptr(), int(i_d.numel()),
                                                                  self._stream()))
 
     # validation iterator (memory.py:162-180)
@@ -521,145 +416,6 @@ class ReplayMemory:
         if n and (int(idx.min()) < 0 or int(idx.max()) >= self.capacity):
             raise IndexError("states_at: index out of range")
         out = torch.empty(n, self.history, 84, 84, dtype=torch.float32, device=self.device)
-        self._idx_keep = idx
+        self._keep["idx"] = idx
         L.check(self._lib, self._lib.rb_replay_states_at(self._handle, idx.data_ptr(), n, out.data_ptr(), self._stream()))
         return out
-
-    # ------------------------------------------------------------------ streaming dump / restore
-    _COLUMNS = ("tree", "frames", "timestep", "action", "reward", "nonterminal")
-
-    def _column_spec(self):
-        b = L.ReplayBuffers()
-        L.check(self._lib, self._lib.rb_replay_buffers(self._h, C.byref(b)))
-        cap = self.capacity
-        return b, {"tree": (b.sum_tree_dev, b.tree_len * 4), "frames": (b.frames_dev, cap * 7056),
-                   "timestep": (b.timestep_dev, cap * 4), "action": (b.action_dev, cap * 4),
-                   "reward": (b.reward_dev, cap * 4), "nonterminal": (b.nonterminal_dev, cap)}
-
-    def save_to(self, fileobj, chunk_bytes=64 << 20):
-        """Streams the replay to a binary file object in `chunk_bytes` pieces (64 MB of host staging instead of the 7 GB
-        a pickle of a 1M-capacity memory needs; main.py:94-100 `pickle.dump(memory, bz2 file)` still works through
-        __getstate__, this is the scalable alternative: `with bz2.open(path, 'wb') as f: mem.save_to(f)`)."""
-        import json
-        import struct
-        b, spec = self._column_spec()
-        hdr = self._header()
-        self.stream_t             # (fetches the device-resident counters after device rounds; refreshes self.t)
-        meta = dict(version=1, capacity=self.capacity, history=self.history, n=self.n, discount=self.discount,
-                    priority_weight=self.priority_weight, priority_exponent=self.priority_exponent, t=self.t,
-                    streams=self.streams, stream_t=[int(x) for x in self.stream_t], seed=self._seed,
-                    augment_pad=int(self.augment_pad), aug_draw=int(self._aug_draw), columns={k: spec[k][1] for k in self._COLUMNS}, header=bytes(hdr).hex())
-        blob = json.dumps(meta).encode()
-        fileobj.write(b"RBRPLY01" + struct.pack("<q", len(blob)) + blob)
-        stage = np.empty(chunk_bytes, dtype=np.uint8)
-        for k in self._COLUMNS:
-            ptr, nbytes = spec[k]
-            for lo in range(0, nbytes, chunk_bytes):
-                m = min(chunk_bytes, nbytes - lo)
-                L.check(self._lib, self._lib.rb_copy_to_host(stage.ctypes.data, ptr + lo, m, self._stream()))
-                fileobj.write(stage[:m].tobytes() if m < chunk_bytes else stage.data)
-
-    @classmethod
-    def load_from(cls, fileobj, device, chunk_bytes=64 << 20):
-        """Inverse of save_to: builds a ReplayMemory on `device` from the stream."""
-        import json
-        import struct
-        import types
-        magic = fileobj.read(8)
-        if magic != b"RBRPLY01":
-            raise ValueError("not a rainbow_amd replay stream")
-        (n,) = struct.unpack("<q", fileobj.read(8))
-        meta = json.loads(fileobj.read(n).decode())
-        args = types.SimpleNamespace(device=device, history_length=meta["history"], discount=meta["discount"],
-                                     multi_step=meta["n"], priority_weight=meta["priority_weight"],
-                                     priority_exponent=meta["priority_exponent"],
-                                     augment_pad=meta.get("augment_pad", 0))                  # (older streams: no augmentation)
-        mem = cls(args, meta["capacity"], seed=meta["seed"], streams=meta.get("streams", 1))   # (older streams: one stream)
-        mem._aug_draw = int(meta.get("aug_draw", 0))
-        mem.t = meta["t"]
-        mem.stream_t = np.array(meta.get("stream_t", [meta["t"]]), dtype=np.int32)
-        b, spec = mem._column_spec()
-        for k in cls._COLUMNS:
-            ptr, nbytes = spec[k]
-            if nbytes != meta["columns"][k]:
-                raise ValueError("replay stream column %s has %d bytes, expected %d" % (k, meta["columns"][k], nbytes))
-            for lo in range(0, nbytes, chunk_bytes):
-                m = min(chunk_bytes, nbytes - lo)
-                buf = fileobj.read(m)
-                if len(buf) != m:
-                    raise EOFError("replay stream truncated in column %s" % k)
-                a = np.frombuffer(buf, dtype=np.uint8)
-                L.check(mem._lib, mem._lib.rb_copy_to_device(ptr + lo, a.ctypes.data, m, mem._stream()))
-        hdr = np.frombuffer(bytes.fromhex(meta["header"]), dtype=np.uint8).copy()
-        L.check(mem._lib, mem._lib.rb_copy_to_device(b.header_dev, hdr.ctypes.data, hdr.nbytes, mem._stream()))
-        return mem
-
-    # ------------------------------------------------------------------ pickling (main.py:94-100,118)
-    def _grab(self, field, start=0, count=None):
-        """Copies rows [start, start+count) of one device column to a numpy array (tests / partial dumps)."""
-        b = L.ReplayBuffers()
-        L.check(self._lib, self._lib.rb_replay_buffers(self._h, C.byref(b)))
-        spec = {"tree": (b.sum_tree_dev, 4, np.float32, b.tree_len), "frames": (b.frames_dev, 7056, np.uint8, self.capacity),
-                "timestep": (b.timestep_dev, 4, np.int32, self.capacity), "action": (b.action_dev, 4, np.int32, self.capacity),
-                "reward": (b.reward_dev, 4, np.float32, self.capacity), "nonterminal": (b.nonterminal_dev, 1, np.uint8, self.capacity)}
-        ptr, row, dtype, rows = spec[field]
-        count = rows - start if count is None else count
-        host = np.empty(count * row, dtype=np.uint8)
-        L.check(self._lib, self._lib.rb_copy_to_host(host.ctypes.data, ptr + start * row, host.nbytes, self._stream()))
-        out = host.view(dtype)
-        return out.reshape(count, 84, 84) if field == "frames" else out
-
-    def _dump(self):
-        b = L.ReplayBuffers()
-        L.check(self._lib, self._lib.rb_replay_buffers(self._h, C.byref(b)))
-        hdr = self._header()
-        cap = self.capacity
-
-        def grab(ptr, nbytes):
-            host = np.empty(nbytes, dtype=np.uint8)
-            L.check(self._lib, self._lib.rb_copy_to_host(host.ctypes.data, ptr, nbytes, self._stream()))
-            return host
-
-        return dict(tree=grab(b.sum_tree_dev, b.tree_len * 4).view(np.float32),
-                    frames=grab(b.frames_dev, cap * 7056), timestep=grab(b.timestep_dev, cap * 4).view(np.int32),
-                    action=grab(b.action_dev, cap * 4).view(np.int32), reward=grab(b.reward_dev, cap * 4).view(np.float32),
-                    nonterminal=grab(b.nonterminal_dev, cap),
-                    header=bytes(hdr))
-
-    def __getstate__(self):
-        dump = self._dump()       # (applies a pending priority write-back first)
-        stream_t = self.stream_t  # (fetches the device-resident counters after device rounds)
-        st = {k: v for k, v in self.__dict__.items()
-              if k not in ("_stream_t_dev", "_stream_t_host", "_dev_round", "_lib", "_h", "_handle", "_pending", "_applied", "_stage", "transitions", "_out", "_uu", "_upd", "_neg_beta_dev",
-                           "_neg_beta_val", "_bufs", "_idx_keep", "_shifts_in")}
-        st["device"] = str(self.device)
-        st["stream_t"] = stream_t
-        st["_dump"] = dump
-        return st
-
-    def __setstate__(self, st):
-        dump = st.pop("_dump")
-        stream_t = st.pop("stream_t", None)
-        self.__dict__.update(st)
-        self.augment_pad = self._checked_pad(st.get("augment_pad", 0))      # (a pickle from before the option: off, draw 0)
-        self._aug_draw = int(st.get("_aug_draw", 0))
-        self.device = torch.device(self.device)
-        self._lib = L.load()
-        # (a pickle from before interleaved streams: one stream)
-        self.stream_t = np.array([self.t], dtype=np.int32) if stream_t is None else np.asarray(stream_t, dtype=np.int32)
-        self._create()
-        b = L.ReplayBuffers()
-        L.check(self._lib, self._lib.rb_replay_buffers(self._h, C.byref(b)))
-        for key, ptr in (("tree", b.sum_tree_dev), ("frames", b.frames_dev), ("timestep", b.timestep_dev),
-                         ("action", b.action_dev), ("reward", b.reward_dev), ("nonterminal", b.nonterminal_dev)):
-            a = np.ascontiguousarray(dump[key])
-            L.check(self._lib, self._lib.rb_copy_to_device(ptr, a.ctypes.data, a.nbytes, self._stream()))
-        hdr = np.frombuffer(dump["header"], dtype=np.uint8).copy()
-        L.check(self._lib, self._lib.rb_copy_to_device(b.header_dev, hdr.ctypes.data, hdr.nbytes, self._stream()))
-        self.transitions = _TransitionsView(self)
-        self._out = {}
-        self._ptr_cache = {}
-        self._pending = None
-        self._stage = {}
-        self._init_beta_source()
-        self._header()   # resynchronise the library's host mirror of index/full

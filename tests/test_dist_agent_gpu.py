@@ -2,7 +2,7 @@
 gloo stages device tensors through the host), each with its own `Agent(args, env)` created under the initialised process
 group and its own HBM replay with different contents.  This drives exactly what `bench.py --gpus N` / `torchrun main.py`
 execute between /root/reference/agent.py:96 and :97: Agent.__init__'s rank-0 broadcast + FactoredExchange, and
-Agent._learn_eager's exchange branch (`self._exchange.run()` / `average_gradients` + the deferred clip + Adam pass).
+Agent._learn_eager's (rainbow_amd/agent_learn.py) exchange branch (`self._exchange.run()` / `average_gradients` + the deferred clip + Adam pass).
 Three learn steps with injected noise and sampler uniforms, both exchange modes: the replicas' parameters must be
 BIT-IDENTICAL, and equal to the oracle fed with the mean of the two replicas' gradients (tolerances of the one-device tests)."""
 import os

@@ -88,3 +88,22 @@ def test_initial_parameters_follow_the_reference_distributions():
                 assert float(v.abs().max()) > 0.95 * bound, name
                 assert abs(float(v.mean())) < 4 * bound / math.sqrt(3 * numel), name
         assert float(flat[~covered].abs().sum()) == 0.0          # alignment padding stays zero
+
+
+def test_every_module_imports_and_the_agent_module_keeps_its_names():
+    """The host layer is split by concern (agent_learn / agent_act / agent_state / params / _util, memory_append /
+    memory_state); tests, tools and the loops keep importing these names from rainbow_amd.agent."""
+    import importlib
+    import inspect
+    import os
+    import rainbow_amd
+    names = sorted(f[:-3] for f in os.listdir(os.path.dirname(rainbow_amd.__file__)) if f.endswith(".py") and f != "__init__.py")
+    assert {"_util", "params", "agent", "agent_learn", "agent_act", "agent_state", "memory", "memory_append", "memory_state"} <= set(names)
+    for name in names:
+        importlib.import_module("rainbow_amd." + name)
+    from rainbow_amd import _util, agent, params
+    assert agent._query_layout is params._query_layout and agent.init_parameters_flat is params.init_parameters_flat
+    assert agent.current_stream_handle is _util.current_stream_handle
+    assert isinstance(inspect.getattr_static(agent.Agent, "_recover_eps_in"), staticmethod)
+    for method in ("learn", "act", "act_batch", "evaluate_q", "state_dict", "load_state_dict", "checkpoint", "restore", "save"):
+        assert callable(getattr(agent.Agent, method)), method

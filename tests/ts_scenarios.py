@@ -111,7 +111,7 @@ def public_sample_after_early_draw_check(lib, Mem, monkeypatch, preceding):
     """with RB_OPTS spec_draw=1, `preceding` back-to-back rb_learner_train_step calls at constant beta leave a
     tentative draw in flight in the replay's OTHER window table.  A caller that then issues the step's entry points one by one —
     rb_replay_sample_fused_noise + rb_learner_learn_windows(rb_replay_buffers_t.window_dev) + rb_learner_clip_adam, what
-    Agent._learn_eager does with the cached frame_source() pointer — must get the windows of ITS draw in table 0: the public
+    Agent._learn_eager (rainbow_amd/agent_learn.py) does with the cached frame_source() pointer — must get the windows of ITS draw in table 0: the public
     sample entry points never accept the tentative draw (only rb_learner_train_step does, which resolves the current table
     itself).  Twin with spec_draw=0; an odd and an even number of preceding steps (the live table alternates), everything
     bit-identical, and one more train_step afterwards."""
