@@ -134,7 +134,7 @@ class Agent(AgentLearn, AgentAct, AgentState):
         self._q_pin = torch.zeros(2 * self.batch_size, dtype=torch.float32).pin_memory()
         self._act_np, self._q_np = self._act_pin.numpy(), self._q_pin.numpy()
         # the single-state path (act / evaluate_q): (action, q) as ONE 8-byte pinned pair — the head stores both with a single
-        # system-scope store (csrc/act_path.h rb_head_act_body) instead of q, a fence, then the action
+        # system-scope store (csrc/act_head.h rb_head_act_body) instead of q, a fence, then the action
         self._aq_pin = torch.zeros(2, dtype=torch.int32).pin_memory()
         self._aq_act = self._aq_pin.numpy()
         self._aq_q = self._aq_act.view(np.float32)

@@ -1,10 +1,10 @@
-// act_host.h — host side of Agent.act / evaluate_q: the one-launch act path (act_path.h) and the batched forward + head
-// (act_batch_run, behind the three rb_learner_act_batch* entry points).
+// act_host.h — host side of Agent.act / evaluate_q: the act path of one state (act_path.h k_act_fused, as one launch or as one
+// launch per phase) and the batched forward + head (act_batch_run, behind the three rb_learner_act_batch* entry points).
 // Included by learner.hip only, after fc_dispatch.h (forward, fc_rows_fwd, nl_h / nl_z) and head.h (k_head_act, k_head_act_eps).
 #pragma once
 #include "learner_internal.h"
 
-// Output rows per workgroup of each conv layer on the act path (act_path.h k_act_conv / k_act_fused): at most RB_ACT_MAXPOS
+// Output rows per workgroup of each conv layer on the act path (act_conv.h rb_act_conv_unit): at most RB_ACT_MAXPOS
 // positions, and the rows' input patch within RB_ACT_LDS floats.  false = a layer the act path does not cover (no row fits, or a
 // filter beyond RB_ACT_KMAX taps).  rb_debug_launch_plan prints the same numbers (act_path rg=).
 static bool act_conv_rows(const Layout& L, int rg[3]) {
@@ -28,8 +28,7 @@ static bool act_path_covers(const Layout& L, const LearnerCaps& caps, int rg[3])
 
 // One state through the act path (act_path.h).  RB_ERR_STATE (without touching the error string) = geometry not
 // covered, the caller falls back to the training kernels.
-// Returns RB_OK (logits ready: the caller launches the head), 1 (the one-launch path ran the head as well and wrote
-// head_action_out / head_q_out), or an error.
+// Returns 1 (the forward AND the head ran, in either launch form, and wrote head_action_out / head_q_out), or an error.
 static int act_forward_single(rb_learner* l, const float* state_dev, const NetPtrs& on, int noisy, hipStream_t stream,
                               int32_t* head_action_out, float* head_q_out) {
   const Layout& L = l->L;
@@ -52,45 +51,41 @@ static int act_forward_single(rb_learner* l, const float* state_dev, const NetPt
   ActFcArgs& z = f.z;
   z.x = l->h; z.w = nl_z(on); z.K = L.H; z.n_rows = L.NZ; z.split_row = L.Z; z.x_off1 = L.H; z.ein_off1 = L.H;
   z.out = l->logits; z.relu = 0; z.mu_only = noisy ? 0 : 1;
-  bool can_fuse = l->opt.act_fused != 0;
-  // (a captured launch would replay a stale launch number: under stream capture the per-layer launches below run instead)
-  if (can_fuse && rb_stream_capturing(stream)) can_fuse = false;
-  if (can_fuse) {
-    // ONE persistent launch (act_path.h k_act_fused): G workgroups, one per CU, all resident — the in-launch waits need that
-    f.Z = L.Z; f.A = L.A; f.logits = l->logits; f.support = l->support; f.action_out = head_action_out; f.q_out = head_q_out;
-    f.ctr = l->act_ctr; f.err = l->act_ctr + 6 * RB_FAN_SHARDS * RB_FAN_STRIDE;
-    int G = (l->n_cu < 256 ? l->n_cu : 256) / RB_FAN_SHARDS * RB_FAN_SHARDS;       // a multiple of the counter shards
-    if (G < RB_FAN_SHARDS) G = RB_FAN_SHARDS;
+  f.Z = L.Z; f.A = L.A; f.logits = l->logits; f.support = l->support; f.action_out = head_action_out; f.q_out = head_q_out;
+  f.ctr = l->act_ctr; f.err = l->act_ctr + 6 * RB_FAN_SHARDS * RB_FAN_STRIDE;
+  int G = (l->n_cu < 256 ? l->n_cu : 256) / RB_FAN_SHARDS * RB_FAN_SHARDS;       // a multiple of the counter shards
+  if (G < RB_FAN_SHARDS) G = RB_FAN_SHARDS;
+  // (a captured launch would replay a stale launch number; the host interpreter runs workgroups one after the other, so an
+  // in-launch wait could never be met)
+  bool one_launch = l->opt.act_fused != 0 && !rb_stream_capturing(stream);
 #if defined(RB_HOST_INTERP)
-    // the host interpreter runs workgroups one after the other: one launch per phase (no in-launch dependency), same bodies
-    for (int ph = 0; ph < 6; ++ph) {
-      if (ph < 3 && ph >= L.nconv) continue;
-      f.phase_lo = ph; f.phase_hi = ph + 1; f.epoch = 0;
-      RB_LAUNCH(k_act_fused<0>, dim3((unsigned)G), dim3(256), stream, f);
-    }
-#else
+  one_launch = false;
+#endif
+  if (one_launch) {
+    // ONE persistent launch: G workgroups, one per CU, all resident — the in-launch waits need that
     f.phase_lo = 0; f.phase_hi = 6; f.epoch = l->act_epoch + 1;        // (counted below, once the launch is in the stream)
     const int hq = (int)rb_div_up(L.F, 256);
     if (hq <= 3) { RB_LAUNCH_T("act:k_act_fused", k_act_fused<3>, dim3((unsigned)G), dim3(256), stream, f); }
     else if (hq <= 13) { RB_LAUNCH_T("act:k_act_fused", k_act_fused<13>, dim3((unsigned)G), dim3(256), stream, f); }
     else { RB_LAUNCH_T("act:k_act_fused", k_act_fused<0>, dim3((unsigned)G), dim3(256), stream, f); }
-#endif
     RB_LAUNCH_CHECK();
-#if !defined(RB_HOST_INTERP)
     ++l->act_epoch;       // only a launch that went out advances the monotonic arrival targets (a refused one signalled nothing)
-#endif
-    return 1;                                              // the head ran inside the launch
+    return 1;
   }
-  for (int layer = 0; layer < L.nconv; ++layer) {
-    const ConvLayer& c = L.conv[layer];
-    RB_LAUNCH(k_act_conv, dim3((unsigned)c.cout, (unsigned)rb_div_up(c.oh, rg[layer])), dim3(256), stream, f.conv[layer]);
+  // One launch per phase: the same kernel, the same units in the same order, the stream orders the phases.  With phase_hi -
+  // phase_lo == 1 a launch of k_act_fused is complete and dependency-free:
+  //   - `fused` is false, so nothing is prefetched;
+  //   - prev == -1, so nothing waits;
+  //   - phase + 1 == phase_hi, so nothing signals (act_epoch is not advanced);
+  //   - epoch == 0 switches off the head's error-word check;
+  //   - ctr and err are never dereferenced.
+  for (int ph = 0; ph < 6; ++ph) {
+    if (ph < 3 && ph >= L.nconv) continue;
+    f.phase_lo = ph; f.phase_hi = ph + 1; f.epoch = 0;
+    RB_LAUNCH(k_act_fused<0>, dim3((unsigned)G), dim3(256), stream, f);
     RB_LAUNCH_CHECK();
   }
-  RB_LAUNCH(k_act_fc, dim3((unsigned)rb_div_up(h.n_rows, 4)), dim3(256), stream, h);
-  RB_LAUNCH_CHECK();
-  RB_LAUNCH(k_act_fc, dim3((unsigned)rb_div_up(z.n_rows, 4)), dim3(256), stream, z);
-  RB_LAUNCH_CHECK();
-  return RB_OK;
+  return 1;
 }
 
 extern "C" {
@@ -105,9 +100,9 @@ int rb_learner_act(rb_learner_t* l, const float* state_dev, int32_t noisy, int32
   src.f32 = state_dev; src.B = 1;
   const NetPtrs on = net_ptrs(L, l->p_online, noisy ? l->n_online : l->zero_noise);
   int rc = act_forward_single(l, state_dev, on, noisy, (hipStream_t)stream, action_dev, q_dev);
-  if (rc == 1) return RB_OK;                                                          // one launch, head included
-  if (rc == RB_ERR_STATE) rc = forward(l, 1, 0, src, on, on, (hipStream_t)stream);   // geometry outside the act path
-  if (rc != RB_OK) return rc;
+  if (rc == 1) return RB_OK;                                                          // the act path, head included
+  if (rc == RB_ERR_STATE) rc = forward(l, 1, 0, src, on, on, (hipStream_t)stream);   // geometry outside the act path:
+  if (rc != RB_OK) return rc;                                                         // the training forward, then the head
   RB_LAUNCH(k_head_act, dim3(1), dim3(256), stream, L.Z, L.A, (const float*)l->logits, 0, (const float*)l->support,
             action_dev, q_dev);
   RB_LAUNCH_CHECK();
@@ -149,7 +144,7 @@ int rb_learner_act_wait(rb_learner_t* l, const float* state_dev, int32_t noisy, 
     // tagged with the launch number, so the next launch starts clean: once more, then give up
     if (++attempts >= 2) {
       rb_set_error("rb_learner_act_wait: the one-launch act path reported an expired in-launch wait twice (action %d); "
-                   "RB_OPTS=act_fused=0 selects the per-layer launches", (int)a);
+                   "RB_OPTS=act_fused=0 selects one launch per phase", (int)a);
       return RB_ERR_STATE;
     }
   }

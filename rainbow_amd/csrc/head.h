@@ -1,6 +1,7 @@
 // head.h — the C51 head of the learn step (k_head) and of Agent.act (k_head_act).  Included by learner.hip only.
 #pragma once
 #include "learner_internal.h"
+#include "act_head.h"
 #include "kernel_stamp.h"
 
 // ------------------------------------------------------------------------- head --
@@ -261,7 +262,7 @@ __global__ __launch_bounds__(RB_HEAD_THREADS) void k_head(int B, int Z, int A, c
   RB_WGT(7, b, 6);
 }
 
-// Agent.act / evaluate_q head (agent.py:53-55, 110-112) for ONE image at logits row `row` (act_path.h rb_head_act_body).
+// Agent.act / evaluate_q head (agent.py:53-55, 110-112) for ONE image at logits row `row` (act_head.h rb_head_act_body).
 __global__ __launch_bounds__(256) void k_head_act(int Z, int A, const float* logits, int row, const float* support,
                                                    int32_t* action_out, float* q_out) {
   __shared__ float s_mean[RB_MAX_ATOMS];

@@ -2,7 +2,7 @@
 // (one slot per phase of a launch's first / last workgroup, g_cstamp), RB_WGT (the per-workgroup timeline, g_wgt) and RB_SPAN (the
 // span of a launch's tenants, g_span); in the product build every macro is ((void)0).  learner.hip defines the three arrays and
 // reads them back.  Included directly by every header whose kernels stamp: conv_fwd.h, conv_dx.h, conv_dw.h, fc_gemm.h, nl_dx.h,
-// nl_bwd.h, head.h, act_path.h, and by learner.hip.
+// nl_bwd.h, head.h, act_path.h (whose bodies in act_conv.h, act_fc.h and act_head.h do not stamp), and by learner.hip.
 #pragma once
 #include "rb_device.h"
 

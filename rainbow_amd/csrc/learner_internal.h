@@ -126,7 +126,7 @@ static const struct { const char* key; int RbOpts::*field; int dflt; const char*
   {"fc_gemm", &RbOpts::fc_gemm, -1, "hidden layer on the LDS-tiled GEMMs of fc_gemm.h: -1 = by shape (from 128 rows per net on), 1 = always, 0 = never"},
   {"implicit_small", &RbOpts::implicit_small, 0, "test hook: RB_LEARNER_IMPLICIT_SIGMA on hidden layers of any size"},
   {"xs", &RbOpts::xs, 0, "row splits of the hidden layer's input gradient: 0 = derived from the hidden size (ceil(2H / 256), at most 4)"},
-  {"act_fused", &RbOpts::act_fused, 1, "Agent.act as ONE launch (0: the per-layer launches)"},
+  {"act_fused", &RbOpts::act_fused, 1, "Agent.act as ONE launch (0: the same kernel, one launch per phase)"},
   {"spec_draw", &RbOpts::spec_draw, 0, "the early draw (opt-in: only append-free loops ever arm it)"},
   {"spec_stall", &RbOpts::spec_stall, 0, "test hook: the early draw's go flag is never stored, the gate in front of the pair expires"},
   {"img_fast", &RbOpts::img_fast, 1, "image-fastest block order of the conv launches (0: the order that image counts off a multiple of 8 get)"},

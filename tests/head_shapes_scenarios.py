@@ -1,4 +1,4 @@
-"""The C51 head (csrc/head.h k_head<ZI>, act_path.h rb_head_act_body) and the output layer in front of it over the accepted
+"""The C51 head (csrc/head.h k_head<ZI>, act_head.h rb_head_act_body) and the output layer in front of it over the accepted
 (atoms, actions) range: one learn body and one act body, run on the host interpreter (test_head_shapes_emu.py) and on the
 device (test_head_shapes_gpu.py) through the C ABI.  Every row of the table is the smallest shape on its side of a boundary.
 
@@ -234,8 +234,10 @@ def _same(got_a, got_q, want, what):
 
 
 def check_act(lib, mem, case, monkeypatch):
-    """Three states, noisy and eval mode: rb_learner_act (one launch, and per-layer launches with RB_OPTS act_fused=0),
-    rb_learner_act_batch, rb_learner_act_batch_eps at epsilon 0, rb_learner_act_batch_rows — each (action, q) against O.act."""
+    """Three states, noisy and eval mode: rb_learner_act (as one launch, and with RB_OPTS act_fused=0 as one launch per phase of
+    the same kernel; the two also against each other, bit for bit — on the host interpreter both run one launch per phase, so
+    there that holds by construction), rb_learner_act_batch, rb_learner_act_batch_eps at epsilon 0, rb_learner_act_batch_rows —
+    each (action, q) against O.act."""
     c, seed = case_config(case)
     cfg, params, raw_shared, raw_rows, states = act_inputs(c, seed)
     ora = act_oracle(case)
@@ -255,9 +257,15 @@ def check_act(lib, mem, case, monkeypatch):
         st = m.upload(states)
         for noisy in (1, 0):
             want = ora["noisy" if noisy else "eval"]
+            got = []
             for x, what in ((ad, "rb_learner_act"), (unfused, "rb_learner_act act_fused=0")):
                 single = [x.act(s, bool(noisy)) for s in states]
-                _same([s[0] for s in single], [s[1] for s in single], want, "%s noisy=%d" % (what, noisy))
+                got.append(([s[0] for s in single], np.asarray([s[1] for s in single], dtype=np.float32)))
+                _same(got[-1][0], got[-1][1], want, "%s noisy=%d" % (what, noisy))
+            # the two launch forms run the same bodies in the same order: equal actions, q equal as 32-bit words
+            assert got[0][0] == got[1][0], ("noisy=%d" % noisy, got[0][0], got[1][0])
+            assert np.array_equal(got[0][1].view(np.uint32), got[1][1].view(np.uint32)), \
+                ("noisy=%d: q of one launch / of one launch per phase" % noisy, [float(v).hex() for v in got[0][1]], [float(v).hex() for v in got[1][1]])
             a, q = ad.act_batch(states, bool(noisy))
             _same(a, q, want, "rb_learner_act_batch noisy=%d" % noisy)
             a, q, e = m.upload(np.full(N_STATES, -3, np.int32)), m.empty((N_STATES,), np.float32), m.empty((N_STATES,), np.uint8)

@@ -232,10 +232,18 @@ def _same(got_a, got_q, want, what):
                                err_msg="%s: q" % what)
 
 
+def _same_bits(one, phases, what):
+    """The two launch forms of rb_learner_act run the same bodies in the same order: equal actions, q equal as 32-bit words."""
+    assert list(one[0]) == list(phases[0]), "%s: one launch chose %s, one launch per phase %s" % (what, list(one[0]), list(phases[0]))
+    assert np.array_equal(one[1].view(np.uint32), phases[1].view(np.uint32)), \
+        "%s: q of one launch %s, of one launch per phase %s" % (what, [x.hex() for x in one[1].astype(float)], [x.hex() for x in phases[1].astype(float)])
+
+
 def check_act(lib, mem, case, monkeypatch, where="hip"):
-    """Three states, noisy and eval mode: rb_learner_act (one launch, and per-layer launches with RB_OPTS act_fused=0),
-    rb_learner_act_batch at n = 3, rb_learner_act_batch_rows at n = 3 under three noise rows — each (action, q) against O.act,
-    one row at a time."""
+    """Three states, noisy and eval mode: rb_learner_act (as one launch, and with RB_OPTS act_fused=0 as one launch per phase of
+    the same kernel — each against the oracle, and the two against each other bit for bit), rb_learner_act_batch at n = 3,
+    rb_learner_act_batch_rows at n = 3 under three noise rows — each (action, q) against O.act, one row at a time.  On the host
+    interpreter both learners run one launch per phase, so the bit comparison there holds by construction."""
     cfgd, seed = case_config(case), CASES[case].seed
     cfg, params, raw_shared, raw_rows, states = act_inputs(cfgd, seed)
     ora = act_oracle(case)
@@ -263,9 +271,12 @@ def check_act(lib, mem, case, monkeypatch, where="hip"):
         st = m.upload(states)
         for noisy in (1, 0):
             want = ora["noisy" if noisy else "eval"]
+            got = {}
             for x, name in ((ad, "rb_learner_act"), (unfused, "rb_learner_act act_fused=0")):
                 single = [x.act(s, bool(noisy)) for s in states]
-                _same([s[0] for s in single], [s[1] for s in single], want, "%s %s noisy=%d" % (what, name, noisy))
+                got[name] = ([s[0] for s in single], np.asarray([s[1] for s in single], dtype=np.float32))
+                _same(got[name][0], got[name][1], want, "%s %s noisy=%d" % (what, name, noisy))
+            _same_bits(got["rb_learner_act"], got["rb_learner_act act_fused=0"], "%s noisy=%d" % (what, noisy))
             a, q = ad.act_batch(states, bool(noisy))
             _same(a, q, want, "%s rb_learner_act_batch noisy=%d" % (what, noisy))
         # one noise sample per row, filled from the injected normals as noise_rows_scenarios.RowsContext does
