@@ -721,7 +721,17 @@ int rb_learner_priority_written(rb_learner_t* l);
  *              rb_learner_clip_adam / rb_learner_clip_grad as usual
  * rb_learner_wait_factors is kept for ABI compatibility and does nothing (the block is complete in stream order).
  * world == 1 (default) restores the single-device step.  [small_offset, +small_floats) still names the conv range for
- * hosts that prefer `allreduce` of the flat gradient + rb_learner_grads_modified.                                     */
+ * hosts that prefer `allreduce` of the flat gradient + rb_learner_grads_modified.
+ * One rank's block is six segments, each rounded up to 64 floats:
+ *   dlogits [B][NZ] | h [B][2H] | dh [B][2H] | feat [B][F] | noise [n_noise] | conv grads [small_floats]
+ * (factor_floats is their total).  The learn call writes the tensors' elements only: the gaps between the segments are never
+ * read, but the alignment padding BETWEEN the conv tensors lies inside the conv segment and is folded (and squared into the
+ * norm) with it — allocate the local block zero-filled, as grads_dev is.
+ * rb_learner_set_exchange refuses with RB_ERR_STATE and a message that points to the `allreduce` route: world outside [1, 64]
+ * (RB_ERR_INVALID), a shape off the streamed noisy-linear kernels (hidden % 32 != 0, hidden > 4096), and a shape whose
+ * rb_learner_finish_grads launch would need more sum-of-squares slots than the 16 384 that exist (8 per 128 x 128 tile of the
+ * hidden layer's weights and per 16-row x 512-column tile of the output layer's, one per hidden-layer tile for the conv range:
+ * canonical, hidden 4096, 18 actions needs 18 368).                                                                     */
 int rb_learner_exchange_layout(rb_learner_t* l, int64_t* factor_floats, int64_t* small_offset, int64_t* small_floats);
 int rb_learner_set_exchange(rb_learner_t* l, int32_t world, float* factors_local_dev, const float* factors_all_dev);
 int rb_learner_wait_factors(rb_learner_t* l, rb_stream_t side_stream);

@@ -148,34 +148,17 @@ __global__ __launch_bounds__(256) void k_sumsq(const float* g, int64_t n, float*
   if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 // rb_learner_finish_grads as ONE launch (three dependent-free jobs would otherwise queue as three ~10 us kernels on the
-// replica step's critical path): block ranges [fc_z dW tiles | fc_h dW tiles | sum of squares of the all-reduced conv range]
+// replica step's critical path): k_finish_grads_tiled below
 struct FinishArgs {
   NlDwArgs z, h;
-  int z_x, z_n, h_x, h_n;      // grid.x and block count of each weight-gradient problem
+  int z_x, z_n;                // grid.x and block count of the output layer's weight-gradient problem
   // conv range: g[i] = (sum over ranks, in rank order, of blocks[r * bstride + i]) * scale; part[b] = this block's sum of squares
   float* g; int64_t n; float* part; int nparts;
   const float* blocks; int64_t bstride; int world; float scale;
 };
-__global__ __launch_bounds__(256) void k_finish_grads(FinishArgs a) {
-  __shared__ float s_red[16];
-  int b = (int)blockIdx.x;
-  if (b < a.z_n) { rb_nl_dw_body_ranks(a.z, b % a.z_x, b / a.z_x, 4 * b); return; }
-  b -= a.z_n;
-  if (b < a.h_n) { rb_nl_dw_body_ranks(a.h, b % a.h_x, b / a.h_x, 4 * b); return; }
-  b -= a.h_n;
-  float acc = 0.0f;
-  for (int64_t i = (int64_t)b * 256 + threadIdx.x; i < a.n; i += (int64_t)a.nparts * 256) {
-    float v = 0.0f;
-    for (int r = 0; r < a.world; ++r) v += a.blocks[(int64_t)r * a.bstride + i];
-    v *= a.scale;
-    a.g[i] = v;
-    acc = fmaf(v, v, acc);
-  }
-  acc = rb_block_sum(acc, s_red);
-  if (threadIdx.x == 0) a.part[b] = acc;
-}
-// The same launch with the hidden layer's weight gradient on 128 x 128 LDS tiles (fc_gemm.h rb_fc_gemm_dw_ranks; 512-thread
-// workgroups): block ranges [fc_h tiles | fc_z 16-row tiles (first four waves) | conv range]
+// The hidden layer's weight gradient on 128 x 128 LDS tiles (fc_gemm.h rb_fc_gemm_dw_ranks; 512-thread workgroups), the output
+// layer's on 16-row tiles of 512 columns (nl_dw.h rb_nl_dw_body_ranks, all eight waves): block ranges [fc_h tiles, each with its
+// slice of the conv range | fc_z tiles]
 __global__ __launch_bounds__(RB_TG_THREADS) void k_finish_grads_tiled(FinishArgs a, int h_nt, int h_kt) {
   __shared__ __attribute__((aligned(16))) float lds[RB_TG_LDS];
   __shared__ float s_red[16];

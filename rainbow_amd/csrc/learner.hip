@@ -230,7 +230,7 @@ int rb_learner_create(rb_learner_t** out, const rb_learner_config_t* cfg, float*
   RB_ALLOC(l->support, (int64_t)L.Z);
   RB_ALLOC(l->zero_noise, L.n_noise);
   RB_ALLOC(l->noise_snap, L.n_noise);
-  RB_ALLOC(l->norm_part, 16384);
+  RB_ALLOC(l->norm_part, RB_NORM_PART_SLOTS);
   RB_ALLOC(l->noise_ctr, 4);
   RB_ALLOC(l->status_copy, 4);
   RB_ALLOC(l->adam_args_dev, (sizeof(ClipAdamArgs) + 3) / 4);

@@ -6,6 +6,9 @@
 #pragma once
 #include "learner_internal.h"
 
+// floats of rb_learner::norm_part: the sum-of-squares partials one step may leave for the clip (plan_fc_bwd fuse_norm, exchange_host.h plan_finish)
+#define RB_NORM_PART_SLOTS 16384
+
 struct PlanIn {
   const Layout& L;
   const RbOpts& opt;
@@ -480,7 +483,7 @@ static FcBwdPlan plan_fc_bwd(const PlanIn& in, bool spec) {
   int64_t conv_out = 0;
   for (int layer = 0; layer < L.nconv; ++layer) conv_out += (int64_t)L.conv[layer].cout * (L.conv[layer].K() + 1);
   p.c_slots = (int)rb_div_up(conv_out, 64);
-  p.fuse_norm = !exch && p.z.slots + p.h.slots + p.c_slots <= 16384;
+  p.fuse_norm = !exch && p.z.slots + p.h.slots + p.c_slots <= RB_NORM_PART_SLOTS;
   p.defer_dw = (in.flags & RB_LEARNER_FUSE_FC_H_DW) && p.pipe && p.h_ct > 0 && p.fuse_norm && in.caps.fast_conv;
   // RB_LEARNER_IMPLICIT_SIGMA: g_sigma = g_mu * (eps_out x eps_in) is left to the optimiser pass (its square still enters
   // the norm here).  Needs the pipelined weight-gradient body (batch <= 32) or the tiled GEMM (batch >= 128), the fused norm and

@@ -1,9 +1,9 @@
 """GPU parity of BASELINE config 5's exchange kernels on ONE device (no RCCL needed): N learner handles stand for N
 replicas (own batch, own noise, identical parameters) — N = 2, and N = 8 = config 5's world size (M = 8 x 32 = 256 gathered
-rows, scale 1/8, the 8-block rank-order fold of k_finish_grads); the collectives are replaced by device-side copies — a torch.cat
+rows, scale 1/8, the 8-block rank-order fold of k_finish_grads_tiled); the collectives are replaced by device-side copies — a torch.cat
 for the all-gather of the per-rank blocks, an elementwise mean for the flat all-reduce — so that what runs on the GPU is exactly
 rb_learner_learn with the exchange armed (k_pack_factors, deferred FC weight gradients), rb_learner_finish_grads
-(k_finish_grads) and, in the 'allreduce' mode, rb_learner_grads_modified -> k_sumsq, followed by the one-pass clip + Adam.
+(k_finish_grads_tiled) and, in the 'allreduce' mode, rb_learner_grads_modified -> k_sumsq, followed by the one-pass clip + Adam.
 Insert point in the reference: between agent.py:96 (backward) and agent.py:97 (clip_grad_norm_).
 Required: both handles bit-identical, and gradients / parameters == the oracle fed with the MEAN gradient."""
 import ctypes as C

@@ -292,6 +292,51 @@ def test_replica_exchange_defers_the_fc_weight_gradients(emu):
     assert p["fc_h_bwd"]["fuse_norm"] == 0 and p["fc_h_bwd"]["implicit_sigma"] == 0 and p["fc_z_bwd"]["pipe"] == 0
 
 
+# table B of tests/exchange_scenarios.py, world 2: what each row reaches with the exchange armed (tag.field: value, as below)
+EXCHANGE_PINS = {
+    "e-d-w2": {"fc_z_bwd.kernel": "k_nl_bwd<true>", "fc_z_bwd.z_tall": 1, "fc_h_bwd.kernel": "k_nl_bwd<false>", "fc_h_fwd.kernel": "k_nl_fwd3<2>",
+               "fc_h_bwd.hsplits": 1, "fc_h_bwd.lazy_dfeat": 1, "head.kernel": "k_head<1>"},
+    "e-d-w3-b33": {"fc_z_bwd.kernel": "k_nl_bwd<false>", "fc_z_bwd.z_tall": 0, "fc_h_bwd.kernel": "k_nl_bwd<false>", "fc_h_fwd.kernel": "k_nl_fwd3<2>"},
+    "e-d-w2-b129": {"fc_z_bwd.kernel": "k_nl_bwd<false>", "fc_z_bwd.z_tall": 0, "fc_h_bwd.kernel": "k_nl_bwd<false>", "fc_h_bwd.gemm_bwd": 0,
+                    "fc_h_fwd.kernel": "k_fc_gemm_fwd", "fc_h_bwd.dx": (9, 1, 3)},
+    "e-d-w2-h160": {"fc_z_bwd.kernel": "k_nl_bwd<true>", "fc_h_bwd.kernel": "k_nl_bwd<false>", "fc_h_fwd.kernel": "k_nl_fwd3<2>", "fc_h_bwd.hsplits": 2,
+                    "fc_h_bwd.lazy_dfeat": 1},
+    "e-c-w2": {"fc_z_bwd.kernel": "k_nl_bwd<true>", "fc_h_bwd.kernel": "k_nl_bwd<false>", "fc_h_fwd.kernel": "k_nl_fwd3<2>", "caps.fast_conv": 1,
+               "conv_dw_all.kernel": "k_conv_dw_all<3>"},
+    "e-c-w2-hist8": {"fc_z_bwd.kernel": "k_nl_bwd<true>", "fc_h_bwd.kernel": "k_nl_bwd<false>", "fc_h_fwd.kernel": "k_nl_fwd3<2>", "caps.fast_conv": 0,
+                     "conv1_fwd.kernel": "k_gemm<ConvFwdProb<GeomC1>>", "feat_block_copy.kernel": "k_block_copy", "dfeat_finish.splits": 1,
+                     "fc_h_bwd.lazy_dfeat": 0},
+    "e-d-w2-z65-a8": {"fc_z_bwd.kernel": "k_nl_bwd<true>", "fc_h_bwd.kernel": "k_nl_bwd<false>", "fc_h_fwd.kernel": "k_nl_fwd3<2>", "head.kernel": "k_head<2>"},
+}
+
+
+def exchange_plan(lib, case, flags=0):
+    import exchange_scenarios as ES
+    c = ES.case_config(case)
+    return plan(lib, batch=c["batch"], atoms=c["atoms"], actions=c["actions"], history=c["history"], hidden=c["hidden"],
+                architecture=0 if c["architecture"] == "canonical" else 1, flags=flags, world=2, cap=1 << 15)
+
+
+def test_every_row_of_the_exchange_learn_table_is_pinned():
+    import exchange_scenarios as ES
+    assert set(EXCHANGE_PINS) == set(ES.LEARN_CASES)
+
+
+@pytest.mark.parametrize("case", sorted(EXCHANGE_PINS))
+def test_exchange_learn_table_reaches_what_each_row_claims(emu, case):
+    """Every row: k_pack_factors in the step, no weight-gradient tiles in either backward launch, no pipelined body, tiled backward
+    GEMM, fused norm or implicit sigma — and the flags Agent sets on one device change nothing."""
+    import exchange_scenarios as ES
+    p = exchange_plan(emu, case)
+    assert "pack_factors" in p and p["fc_z_bwd"]["dw"] == (0, 0) and p["fc_h_bwd"]["dw"] == (0, 0), (case, p["fc_z_bwd"], p["fc_h_bwd"])
+    assert p["fc_z_bwd"]["pipe"] == 0 and p["fc_h_bwd"]["gemm_bwd"] == 0 and p["fc_h_bwd"]["fuse_norm"] == 0
+    assert p["fc_h_bwd"]["implicit_sigma"] == 0 and p["fc_h_bwd"]["defer_dw"] == 0
+    for key, want in EXCHANGE_PINS[case].items():
+        tag, _, field = key.partition(".")
+        assert tag in p and p[tag][field] == want, (case, key, p.get(tag), want)
+    assert exchange_plan(emu, case, flags=ES.AGENT_FLAGS) == p
+
+
 def test_bad_arguments_are_refused_with_a_message(emu):
     cfg = _lib.LearnerConfig(batch=32, atoms=51, actions=6, history=4, hidden=512, architecture=0, multi_step=3, v_min=-10.0,
                              v_max=10.0, discount=0.99)

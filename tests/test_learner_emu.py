@@ -589,7 +589,7 @@ def test_large_batch_fc_backward_matches_oracle(emu, monkeypatch):
 def test_replica_exchange_kernels_fold_more_than_two_blocks(emu, world):
     """The replica exchange of SURVEY 8(e) (insert point agent.py:96-97) with MORE than two replicas on the host interpreter:
     `world` learner handles with their own batch and noise, k_pack_factors in every learn call, a host concatenation for the
-    all-gather, k_finish_grads folding `world` blocks in rank order (M = world x B gathered rows, scale 1 / world), then
+    all-gather, k_finish_grads_tiled folding `world` blocks in rank order (M = world x B gathered rows, scale 1 / world), then
     clip + Adam: every handle bit-identical, gradients and parameters == the oracle fed with the mean of the `world`
     gradients.  (World 8 — BASELINE config 5 — runs at the canonical H = 512 / B = 32 shape on the GPU, tests/test_exchange_gpu.py.)"""
     import ctypes as C

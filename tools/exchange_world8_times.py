@@ -1,7 +1,7 @@
 """usage: python tools/exchange_world8_times.py <kernel_stats.csv> — per-kernel durations of the replica exchange measured on
 ONE device: rocprofv3 --kernel-trace --stats over tests/test_exchange_gpu.py's world-8 case (8 learner handles standing for 8
 replicas, cfg-2 shape: the all-gather is a device-side copy there).  What one GPU can measure of config 5's step: k_pack_factors
-(this rank's 1.02 MB block), k_finish_grads (the 8-block rank-order fold, M = 256 gathered rows) and the clip + Adam pass behind it."""
+(this rank's 1.02 MB block), k_finish_grads_tiled (the 8-block rank-order fold, M = 256 gathered rows) and the clip + Adam pass behind it."""
 import csv
 import sys
 

@@ -5,7 +5,10 @@ decisions to the oracle (masked).  --best: all N seeds, and the one whose smalle
 where the first one only just passes).  Prints the margins it saw and the oracle's time for the two steps.
 usage: python tools/ladder_seeds.py --shape-range [case ...] [--seeds N] — the same for tests/shape_range_scenarios.py's table: the first
 seed in [0, N) (default 14) that gives both steps a margin of at least 2.5 x RELU_MARGIN and the act calls their top-two gap; prints the
-row's seed and margins as the table holds them, and 'none' where the row has to be masked."""
+row's seed and margins as the table holds them, and 'none' where the row has to be masked.
+usage: python tools/ladder_seeds.py --exchange [case ...] [--seeds N] — the same for table B of tests/exchange_scenarios.py (the learn step
+with the replica exchange armed): the first seed in [0, N) (default 14) for which every rank, in both steps, has a margin of at least
+2.5 x RELU_MARGIN; the margins printed are the smallest over the ranks."""
 import os
 import sys
 import time
@@ -30,6 +33,24 @@ def margin(run, k):
 
 
 args = sys.argv[1:]
+if "--exchange" in args:
+    import exchange_scenarios as ES  # noqa: E402
+    args.remove("--exchange")
+    n = 14
+    if "--seeds" in args:
+        i = args.index("--seeds")
+        n = int(args[i + 1])
+        del args[i:i + 2]
+    for case in args or list(ES.LEARN_CASES):
+        t0 = time.time()
+        found, seen = ES.find_seed(case, n)
+        tried = "; ".join("%d: %.1e %.1e" % (s, m[0], m[1]) for s, m in seen)
+        if found:
+            print("%-14s seed %d   margins (%.1e, %.1e)   (%.1f s)   seen: %s" % (case, found[0], found[1][0], found[1][1], time.time() - t0, tried),
+                  flush=True)
+        else:
+            print("%-14s seed none: masked   (%.1f s)   seen: %s" % (case, time.time() - t0, tried), flush=True)
+    sys.exit(0)
 if "--shape-range" in args:
     import shape_range_scenarios as SR  # noqa: E402
     args.remove("--shape-range")
