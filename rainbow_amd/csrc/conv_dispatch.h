@@ -52,7 +52,7 @@ static int launch_conv_fwd(rb_learner* l, int layer, int n_on, int n_tg, const I
       if constexpr (!FIRST && C::T16_OK) { RB_LAUNCH_T(tags[layer], (k_conv_fwd_multi_t16<G, NT, PR, KMAX, PCH>), p.grid, block, stream, a); }
       break;
     case CONV_FWD_T16:
-      if constexpr (C::T16_OK) { RB_LAUNCH_T(tags[layer], (k_conv_fwd_t16<G, NT, PR, KMAX, FIRST, PCH, 1>), p.grid, block, stream, a); }
+      if constexpr (C::T16_OK) { RB_LAUNCH_T(tags[layer], (k_conv_fwd_t16<G, NT, PR, KMAX, FIRST, PCH>), p.grid, block, stream, a); }
       break;
     case CONV_FWD_LDS_F32:
       if constexpr (FIRST) { RB_LAUNCH_T(tags[layer], (k_conv_fwd_lds<G, NT, PR, KMAX, FIRST, PCH, FIRST>), p.grid, block, stream, a); }

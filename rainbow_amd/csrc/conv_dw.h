@@ -268,7 +268,7 @@ struct ConvDwAllArgs {
   int cotiles[3];
   int batch;
   int ipb[3];              // images summed per workgroup, per layer (the layers' workgroups cost differently: learner_plan.h plan_conv_dw_all)
-  int img_fast;            // decode with the image group as the FASTEST index (see k_conv_fwd_lds): needs block ranges and group
+  int img_fast;            // decode with the image group as the FASTEST index (see ConvLdsFwdArgs::img_fast, conv_fwd.h): needs block ranges and group
                            // counts that are multiples of 8
 };
 template <class G0, int RC0, class G1, int RC1, int K1, class G2, int RC2, int K2, int NL>

@@ -60,7 +60,7 @@ struct ConvLdsDxArgs {
   int64_t dy_stride;     // floats between partials
   int dy_splits;
   int ipb, batch;        // MULTI instantiation: images per workgroup (grid z = ceil(batch / ipb)), image count
-  int img_fast;          // grid = (image groups, channel tiles, phase x position groups): see k_conv_fwd_lds
+  int img_fast;          // grid = (image groups, channel tiles, phase x position groups): see ConvLdsFwdArgs::img_fast (conv_fwd.h)
 };
 
 // ---- dY of one image for both data-gradient kernels: global loads into registers (issue), LDS stores later (commit) ----------------
@@ -389,14 +389,14 @@ __global__ __launch_bounds__((64 * ConvDxT16<G, COUT>::NWV)) void k_conv_dx_t16_
     __syncthreads();                                    // dY (and the slab) complete
     if (img + 1 < img_end) dyl.issue(a, t, ni, img + 1);
     if (tile_wave) {
-      rb_f32x4 acc[1];
+      rb_f32x4 acc;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) acc[0][r] = 0.0f;
-      rb_t16_steps<Z, WS, 1, 0, KQ / 4>(ap, bp, acc);
+      for (int r = 0; r < 4; ++r) acc[r] = 0.0f;
+      rb_t16_steps<Z, WS, 0, KQ / 4>(ap, bp, acc);
       float* dxi = a.dx + (int64_t)img * a.cin * G::IP;
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (eoff[r] >= 0) dxi[eoff[r]] = mask[r] > 0.0f ? acc[0][r] : 0.0f;
+        if (eoff[r] >= 0) dxi[eoff[r]] = mask[r] > 0.0f ? acc[r] : 0.0f;
     }
     __syncthreads();                                    // every wave is done reading this image's dY
   }

@@ -1,7 +1,7 @@
 // conv_stage.h — what more than one conv kernel shares: the workgroup size, the geometry of the de-interleaved input patch
 // (ConvPatch: SUB, RP, PLANE and the cell function, one constexpr place), the weight-slab staging (rb_wswz, rb_stage_weights_t,
-// rb_slab_copy), the f32 patch commit, the u8 -> x/255 unpack, the lazy dY sum and the whole-K 16x16x4 tile (rb_t16_steps).  Included by
-// conv_fwd.h, conv_dx.h and conv_dw.h.
+// rb_slab_copy), the f32 patch issue and commit, the u8 -> x/255 unpack, the lazy dY sum and the whole-K 16x16x4 tile (rb_t16_steps).
+// Included by conv_fwd.h (for its sections conv_fwd_t16.h, conv_fwd_image.h, conv_fwd_multi.h and conv_fwd_full.h), conv_dx.h and conv_dw.h.
 #pragma once
 #include "learner_problems.h"
 
@@ -100,8 +100,36 @@ struct ConvPatch {
   }
 };
 
-// commit of an f32 patch held in registers (thread t's i-th element is e = i * THREADS + t of the [cin][per_c] patch, per_c = 4 v4)
-// to its de-interleaved cells: quads (IH % 4 == 0) ...
+// An f32 patch through registers: thread t's i-th element is e = i * THREADS + t of the [cin][per_c] patch (per_c = 4 v4) whose rows
+// start `row0` floats into each channel plane of xbase.  Issue (global loads into the registers), as quads (IH % 4 == 0) ...
+// CLAMP: every load is issued, elements beyond the patch at its last index (k_conv_fwd_multi_t16); otherwise they are skipped
+// (ConvFwdBody).  Which of the two a kernel does is its own history: nobody recorded why they differ.
+template <class G, bool CLAMP, int N, int THREADS>
+__device__ __forceinline__ void rb_patch_issue(float4 (&xv)[N], const float* xbase, int row0, int t, int v4, int total4) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const int e = i * THREADS + t;
+    if (CLAMP || e < total4) {
+      const int ec = (!CLAMP || e < total4) ? e : total4 - 1;
+      const int c = ec / v4, q = ec - c * v4;
+      xv[i] = rb_ld4(xbase + (int64_t)c * G::IP + row0 + q * 4);
+    }
+  }
+}
+// ... or single elements
+template <class G, bool CLAMP, int N, int THREADS>
+__device__ __forceinline__ void rb_patch_issue(float (&xs)[N], const float* xbase, int row0, int t, int per_c, int total1) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const int e = i * THREADS + t;
+    if (CLAMP || e < total1) {
+      const int ec = (!CLAMP || e < total1) ? e : total1 - 1;
+      const int c = ec / per_c, q = ec - c * per_c;
+      xs[i] = xbase[(int64_t)c * G::IP + row0 + q];
+    }
+  }
+}
+// Commit (the registers to their de-interleaved cells in LDS): quads ...
 template <class PG, int N, int THREADS>
 __device__ __forceinline__ void rb_patch_commit(float* dst, const float4 (&xv)[N], int t, int v4, int total4) {
   typedef typename PG::G G;
@@ -153,23 +181,17 @@ __device__ __forceinline__ float rb_dy_lazy(float mask, const float (&part)[4], 
 }
 
 // steps [4 JQ0, 4 JQ1) of a lane's quarter of a whole-K 16x16x4 reduction (lane (x = l & 15, kq = l >> 4): row x of the A slab, rows
-// WS apart, its quarter at ap; B cells at the compile-time offsets OFF::at(step) from bp) for CTW row tiles, 16 rows apart, from
-// ONE B operand per step: a ds_read_b128 of each row, four B cells at immediate offsets, four MFMAs per tile
-template <class OFF, int WS, int CTW, int JQ0, int JQ1>
-__device__ __forceinline__ void rb_t16_steps(const float* ap, const float* bp, rb_f32x4 (&acc)[CTW]) {
+// WS apart, its quarter at ap; B cells at the compile-time offsets OFF::at(step) from bp): a ds_read_b128 of the row, four B cells
+// at immediate offsets, four MFMAs
+template <class OFF, int WS, int JQ0, int JQ1>
+__device__ __forceinline__ void rb_t16_steps(const float* ap, const float* bp, rb_f32x4& acc) {
 #pragma unroll
   for (int jq = JQ0; jq < JQ1; ++jq) {
-    float4 w4[CTW];
-#pragma unroll
-    for (int u = 0; u < CTW; ++u) w4[u] = rb_ld4(ap + u * 16 * WS + 4 * jq);
+    const float4 w4 = rb_ld4(ap + 4 * jq);
     const float b0 = bp[OFF::at(4 * jq + 0)], b1 = bp[OFF::at(4 * jq + 1)], b2 = bp[OFF::at(4 * jq + 2)], b3 = bp[OFF::at(4 * jq + 3)];
-#pragma unroll
-    for (int u = 0; u < CTW; ++u) acc[u] = rb_mfma16(w4[u].x, b0, acc[u]);
-#pragma unroll
-    for (int u = 0; u < CTW; ++u) acc[u] = rb_mfma16(w4[u].y, b1, acc[u]);
-#pragma unroll
-    for (int u = 0; u < CTW; ++u) acc[u] = rb_mfma16(w4[u].z, b2, acc[u]);
-#pragma unroll
-    for (int u = 0; u < CTW; ++u) acc[u] = rb_mfma16(w4[u].w, b3, acc[u]);
+    acc = rb_mfma16(w4.x, b0, acc);
+    acc = rb_mfma16(w4.y, b1, acc);
+    acc = rb_mfma16(w4.z, b2, acc);
+    acc = rb_mfma16(w4.w, b3, acc);
   }
 }

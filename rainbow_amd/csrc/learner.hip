@@ -5,7 +5,7 @@
 // Reference being replaced: model.py (NoisyLinear, DQN) and agent.py:61-98.  The reference
 // issues ~1750 framework ops per learn(); here the step is a fixed chain of 14 launches after the sampler
 // (DESIGN.md §3 has the table with what bounds each):
-//   conv fwd x L (conv_fwd.h: operands in LDS, 8 waves split K)
+//   conv fwd x L (conv_fwd.h and its sections conv_fwd_*.h: operands in LDS, 8 waves split K or whole-K tiles)
 //   -> fc_h, fc_z forward (nl_fwd.h k_nl_fwd3: weights streamed once, whole K per block, no partials)
 //   -> head (dueling + softmaxes + double-Q + projection + loss + dlogits, one workgroup per sample, atom bins in LDS)
 //   -> fc_z backward (dW || dX in one launch) -> fc_h backward (dW || dX || the sum-tree priority write-back)
@@ -530,11 +530,14 @@ int rb_learner_sync_target(rb_learner_t* l, rb_stream_t stream) {
 // RB_STAMP builds: what the runtime says about the residency of the first layer's forward kernels
 int rb_debug_occupancy(void) {
   int a = 0, b = 0;
-  hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, (const void*)(k_conv_fwd_t16<GeomC1, 3, 20, 256, true, 80, 1>), 640, 0);
-  hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (const void*)(k_conv_fwd_lds<GeomC1, 3, 20, 256, true, 80>), 512, 0);
+  typedef CfgC1 C;
+  constexpr int T16_THREADS = 64 * ConvFwdWaves<C::KMAX, C::PCH, true>::NWV;
+  const void* t16 = (const void*)(k_conv_fwd_t16<C::G, C::NT, C::PR, C::KMAX, true, C::PCH>);
+  hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, t16, T16_THREADS, 0);
+  hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (const void*)(k_conv_fwd_lds<C::G, C::NT, C::PR, C::KMAX, true, C::PCH>), RB_CONV_THREADS, 0);
   hipFuncAttributes fa;
-  hipFuncGetAttributes(&fa, (const void*)(k_conv_fwd_t16<GeomC1, 3, 20, 256, true, 80, 1>));
-  printf("occupancy API: conv1 t16 (640 threads) %d blocks/CU, conv1 lds (512 threads) %d; t16: regs %d lds %zu maxThreads %d\n", a, b, fa.numRegs, fa.sharedSizeBytes, fa.maxThreadsPerBlock);
+  hipFuncGetAttributes(&fa, t16);
+  printf("occupancy API: conv1 t16 (%d threads) %d blocks/CU, conv1 lds (%d threads) %d; t16: regs %d lds %zu maxThreads %d\n", T16_THREADS, a, RB_CONV_THREADS, b, fa.numRegs, fa.sharedSizeBytes, fa.maxThreadsPerBlock);
   return a;
 }
 #endif

@@ -68,7 +68,7 @@ struct ConvCfg {
   using G = G_;
   static constexpr int NT = NT_, PR = PR_, KMAX = KMAX_, PCH = PCH_;
   static constexpr bool FIRST = FIRST_;
-  // whole-K 16x16x4 tiles, one wave per tile, no cross-wave reduction (conv_fwd.h T16).  Every later layer of the canonical stack
+  // whole-K 16x16x4 tiles, one wave per tile, no cross-wave reduction (conv_fwd_image.h T16).  Every later layer of the canonical stack
   // qualifies (cin * KK == KMAX and cout % 32 == 0 by construction); the data-efficient ones do not (K % 16 != 0, 9 positions)
   static constexpr bool T16_OK = KMAX % 16 == 0 && (KMAX / G::KK) % 4 == 0 && 2 * ((PCH + 15) / 16) <= 16 && (PCH % 16 == 0 || PCH >= G::P) && G::P > 16;
 };
@@ -123,7 +123,7 @@ static ConvFwdPlan plan_conv_fwd_g(const PlanIn& in, int layer, int n_on, int n_
     return p;
   }
   const bool out_blocked = layer == in.L.nconv - 1 && in.caps.fast_fc;
-  // large batches: one round of workgroups, each keeping its weight slab for ipb images of one net (conv_fwd.h)
+  // large batches: one round of workgroups, each keeping its weight slab for ipb images of one net (conv_fwd_multi.h, conv_fwd_full.h)
   const bool multi_forced = in.opt.conv_multi >= 0;
   int ipb = 0;
   if (multi_forced) ipb = in.opt.conv_multi;
@@ -149,7 +149,7 @@ static ConvFwdPlan plan_conv_fwd_g(const PlanIn& in, int layer, int n_on, int n_
         p.img_fast = 1;
         p.grid = dim3(ngroups, (unsigned)rb_div_up(c.cout, 32), (unsigned)rb_div_up(G::P, C::PCH));
       }
-      p.block = 64 * ConvFwdWaves<G, C::NT, C::PR, C::KMAX, false, C::PCH, false, 1>::NWV;
+      p.block = 64 * ConvFwdWaves<C::KMAX, C::PCH, true>::NWV;
       return p;
     }
   }
@@ -162,12 +162,12 @@ static ConvFwdPlan plan_conv_fwd_g(const PlanIn& in, int layer, int n_on, int n_
     // the first layer: u8 frames of a full history only (f32 states — act / evaluate — and history < 4 run the split-K kernel below)
     if (!C::FIRST || (in.opt.t16 && !f32 && c.cin * G::KK == C::KMAX)) {
       // (one channel tile per wave: 2 measured slower for the first layer — 5-wave staging)
-      p.kernel = CONV_FWD_T16; p.block = 64 * ConvFwdWaves<G, C::NT, C::PR, C::KMAX, C::FIRST, C::PCH, false, 1>::NWV;
+      p.kernel = CONV_FWD_T16; p.block = 64 * ConvFwdWaves<C::KMAX, C::PCH, true>::NWV;
       return p;
     }
   }
   // split-K 32x32x2 tiles: first layers (above) and the data-efficient second layer; float states (act / evaluate) have an
-  // instantiation of their own (conv_fwd.h F32SRC)
+  // instantiation of their own (conv_fwd_image.h F32SRC)
   p.kernel = (C::FIRST && f32) ? CONV_FWD_LDS_F32 : CONV_FWD_LDS; p.block = RB_CONV_THREADS;
   return p;
 }

@@ -65,7 +65,7 @@ def test_chunk_fastest_conv_block_order_matches_golden(emu, monkeypatch):
 
 @pytest.mark.parametrize("t16", ["0"], ids=["whole-k-16x16-later-layers-only"])
 def test_conv_forward_tile_variants_match_golden(emu, monkeypatch, t16):
-    """The conv forward's MFMA phase exists twice (conv_fwd.h rb_conv_fwd_body): 32x32x2 tiles with the reduction split over 8
+    """The conv forward's MFMA phase exists twice (conv_fwd_image.h rb_conv_fwd_body): 32x32x2 tiles with the reduction split over 8
     waves + an LDS sum, and (T16) one wave per 16x16 tile over the whole reduction with the epilogue straight from the
     accumulators.  Default: T16 for every canonical layer incl. the u8 first one (what every other test runs); RB_OPTS t16=0 puts
     the first layer alone on the split-K kernel — what a canonical network with history < 4 runs — on the history-4 fixture."""
