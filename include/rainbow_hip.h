@@ -398,6 +398,23 @@ int rb_replay_position(rb_replay_t* r, int64_t* index_host, int32_t* full_host);
  * argument, so main.py:161's per-step annealing works under a captured hipGraph.           */
 int rb_replay_set_beta_source(rb_replay_t* r, const float* neg_beta_dev);
 
+/* Annealed update horizon and discount (BBF: n from 10 down to 3 and gamma from 0.97 up to 0.997 after every reset) on a LIVE replay,
+ * ring and tree untouched.  n_max is the multi_step the handle was created with; 1 <= n_eff <= n_max and 0 < discount <= 1.  From
+ * the next draw on, every output is bit for bit what a replay created with multi_step = n_eff and this discount draws from the same
+ * ring, tree and uniforms (memory.py:111-145 with n = n_eff: the return over k < n_eff, the nonterminal at idx + n_eff, the next
+ * state from window slots [n_eff, n_eff + history), the write-head rule (index - idx) mod capacity > n_eff).
+ *   The stride rule: n_max keeps deciding every allocation and the row stride of the window table — rb_replay_buffers_t.window_len
+ *     stays history + n_max, and a reader addresses row i at window_dev + i * window_len whatever n_eff is.
+ *   The -1 rule: slots [history + n_eff, history + n_max) of every row are written as -1 (the value of a blanked slot), never a
+ *     ring index that may straddle the write head.
+ * gamma^k (float32 of the double power, memory.py:101) is stored in stream order by a one-workgroup launch on `stream` that receives
+ * the table by value: no copy from pageable memory, no synchronisation; a draw already queued on `stream` sees the old table, the
+ * next one the new.  Like every entry point that changes the replay it discards an early draw in flight.  The horizon is a host-side
+ * value of the handle: a captured graph freezes the one in force at capture, as it freezes every by-value argument.
+ * rb_replay_get_horizon reads the host values (n_max and the creation discount until the first set).                            */
+int rb_replay_set_horizon(rb_replay_t* r, int32_t n_eff, double discount, rb_stream_t stream);
+int rb_replay_get_horizon(rb_replay_t* r, int32_t* n_eff_host, double* discount_host);
+
 /* SegmentTree.update (memory.py:44-48): raw leaf values, duplicates last-write-wins. */
 int rb_replay_update_leaves(rb_replay_t* r, const int64_t* tree_idx_dev, const float* values_dev,
                             int32_t n, rb_stream_t stream);
@@ -693,6 +710,15 @@ int rb_learner_pending_launched(rb_learner_t* l);
  * with step = 0 reads the step number from it and forms the bias corrections 1 - beta^t in the kernel (double, one thread
  * per block).  NULL clears.                                                                                           */
 int rb_learner_set_step_counter(rb_learner_t* l, int64_t* step_dev);
+
+/* The learner's side of rb_replay_set_horizon: 1 <= n_eff <= cfg.multi_step, 0 < discount <= 1.  Sets the head's
+ * gamma_n = float32(pow(discount, n_eff)) (agent.py:79) and the next-state slot n_eff + c that the zero-copy conv path reads from a
+ * window-table row; the row stride that rb_learner_learn_windows checks stays history + cfg.multi_step.  Host state read when a step
+ * is launched: no launch, no stream.  rb_learner_train_step* draw the batch themselves and refuse, before anything is launched, when
+ * the replay's (n_eff, discount) differ from the learner's; a caller that samples itself (rb_learner_learn, rb_learner_learn_windows)
+ * keeps the two handles in step.                                                                                          */
+int rb_learner_set_horizon(rb_learner_t* l, int32_t n_eff, double discount);
+int rb_learner_get_horizon(rb_learner_t* l, int32_t* n_eff_host, double* discount_host);
 
 /* Fused priority write-back (agent.py:100 -> memory.py:157-159).  With a sink set, rb_learner_learn*
  * itself applies  sum_tree[tree_idx] = loss^w  (+ ancestor sums, max) to `replay` as one extra

@@ -119,6 +119,10 @@ SIGNATURES = {
     "rb_replay_sample": (c_int, [c_void_p, c_int32, c_double, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rb_replay_set_beta_source": (c_int, [c_void_p, c_void_p]),
+    "rb_replay_set_horizon": (c_int, [c_void_p, c_int32, c_double, c_void_p]),
+    "rb_replay_get_horizon": (c_int, [c_void_p, C.POINTER(c_int32), C.POINTER(c_double)]),
+    "rb_learner_set_horizon": (c_int, [c_void_p, c_int32, c_double]),
+    "rb_learner_get_horizon": (c_int, [c_void_p, C.POINTER(c_int32), C.POINTER(c_double)]),
     "rb_replay_failed_samples": (c_int, [c_void_p, C.POINTER(c_int64)]),
     "rb_replay_reset_failed_samples": (c_int, [c_void_p]),
     "rb_replay_dropped_updates": (c_int, [c_void_p, C.POINTER(c_int64)]),

@@ -52,8 +52,9 @@ class Agent(AgentLearn, AgentAct, AgentState):
         self.support = torch.linspace(args.V_min, args.V_max, self.atoms).to(device=self.device)   # agent.py:18
         self.delta_z = (args.V_max - args.V_min) / (self.atoms - 1)
         self.batch_size = args.batch_size
-        self.n = args.multi_step
+        self.n = args.multi_step                                     # n_max: what the learner handle is created with
         self.discount = args.discount
+        self.horizon = int(args.multi_step)                          # the effective horizon (set_horizon)
         self.norm_clip = args.norm_clip
         self.training = True
 
@@ -256,6 +257,20 @@ class Agent(AgentLearn, AgentAct, AgentState):
             if "step" in st:
                 st["step"].zero_()
         self.resets += 1
+
+    def set_horizon(self, n, discount=None):
+        """The effective multi-step horizon and discount of the targets (rb_learner_set_horizon; BBF anneals n from 10 to 3 and
+        gamma from 0.97 to 0.997 after every reset — rainbow_amd.loop.horizon_at): 1 <= n <= self.n, the multi_step of
+        construction, 0 < discount <= 1, None keeps the current discount.  Host state read when the next step is launched: no
+        launch, no synchronisation.  The replay must be set to the same pair (ReplayMemory.set_horizon): learn() compares."""
+        n = int(n)
+        g = float(self.discount if discount is None else discount)
+        if not 1 <= n <= int(self.n):
+            raise ValueError("set_horizon: n must be in [1, %d] (the multi_step of construction), got %d" % (self.n, n))
+        if not 0.0 < g <= 1.0:                            # (also NaN)
+            raise ValueError("set_horizon: discount must be in (0, 1], got %r" % g)
+        L.check(self._lib, self._lib.rb_learner_set_horizon(self._h, n, g))
+        self.horizon, self.discount = n, g
 
     def flush(self):
         """Run the optimiser pass the last learn() left pending (RAINBOW_AMD_DEFER_UPDATE), if any."""

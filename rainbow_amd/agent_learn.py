@@ -20,6 +20,9 @@ class AgentLearn:
         device-resident and launched eagerly.  The injected-randomness arguments are parity-test hooks."""
         device_mem = isinstance(mem, ReplayMemory)
         if device_mem:
+            if mem.horizon != self.horizon or mem.discount != self.discount:      # (host values: no synchronisation)
+                raise ValueError("Agent.learn: the memory's horizon and discount (%d, %r) differ from the agent's (%d, %r): call "
+                                 "set_horizon on both with the same values" % (mem.horizon, mem.discount, self.horizon, self.discount))
             if self._step_dev is None:
                 # by-value step numbers (RAINBOW_AMD_DEFER_UPDATE=0): the host's step count must be exact BEFORE the next
                 # optimiser pass is issued, so the sampler launches in flight are waited for here (the default mode counts the

@@ -183,6 +183,7 @@ int rb_learner_create(rb_learner_t** out, const rb_learner_config_t* cfg, float*
     for (int i = 0; i < 6; ++i) { l->fact_off[i] = off; off = align64(off + seg[i]); }
     l->fact_stride = off;
   }
+  l->n_eff = cfg->multi_step; l->discount = cfg->discount;
   l->gamma_n = (float)pow(cfg->discount, (double)cfg->multi_step);
   l->delta_z = (float)(((double)cfg->v_max - (double)cfg->v_min) / (double)(cfg->atoms - 1));
   const int B = L.B, NI = 3 * B;
@@ -373,12 +374,20 @@ int rb_learner_learn_windows(rb_learner_t* l, const uint8_t* frames_dev, const i
   }
   ImgSrc src;
   memset(&src, 0, sizeof(src));
-  src.B = l->L.B; src.ring = frames_dev; src.win = windows_dev; src.win_len = window_len; src.n_step = l->cfg.multi_step;
+  src.B = l->L.B; src.ring = frames_dev; src.win = windows_dev; src.win_len = window_len; src.n_step = l->n_eff;
   return learn_impl(l, src, nullptr, actions_dev, returns_dev, nonterminals_dev, weights_dev, loss_dev, (hipStream_t)stream_);
 }
 
 static int train_step_impl(rb_learner_t* l, const rb_train_step_t* a, rb_comm_t* comm, rb_stream_t stream) {
   RB_REQUIRE(l != nullptr && a != nullptr && a->replay != nullptr, "rb_learner_train_step: NULL argument");
+  {   // this call draws the batch itself: targets built from another horizon or discount than the replay's returns are refused
+    int32_t rn = 0;
+    double rg = 0.0;
+    rb_replay_horizon(a->replay, &rn, &rg);
+    RB_REQUIRE(rn == l->n_eff && rg == l->discount, "rb_learner_train_step: the replay's horizon and discount (%d, %.17g) differ from "
+               "the learner's (%d, %.17g): call rb_replay_set_horizon and rb_learner_set_horizon with the same values", (int)rn, rg,
+               (int)l->n_eff, l->discount);
+  }
   // the previous call's optimiser pass, if it was left pending, rides in this call's sampler launch (adam_body.h)
   rb_noise_job_t hosted_job;
   const rb_noise_job_t* job = a->noise_job;
@@ -447,6 +456,23 @@ int rb_learner_train_step_dist(rb_learner_t* l, const rb_train_step_t* a, rb_com
   RB_REQUIRE(comm != nullptr, "rb_learner_train_step_dist: NULL communicator");
   return train_step_impl(l, a, comm, stream);
 }
+// The effective horizon and discount of the targets (include/rainbow_hip.h): host state read when a step is launched, no launch here.
+int rb_learner_set_horizon(rb_learner_t* l, int32_t n_eff, double discount) {
+  RB_REQUIRE(l != nullptr, "rb_learner_set_horizon: NULL handle");
+  RB_REQUIRE(n_eff >= 1 && n_eff <= l->cfg.multi_step, "rb_learner_set_horizon: n_eff must be in [1, %d] (the multi_step the learner "
+             "was created with), got %d", (int)l->cfg.multi_step, (int)n_eff);
+  RB_REQUIRE(discount > 0.0 && discount <= 1.0, "rb_learner_set_horizon: discount must be in (0, 1], got %g", discount);   // (also NaN)
+  l->n_eff = n_eff; l->discount = discount;
+  l->gamma_n = (float)pow(discount, (double)n_eff);
+  return RB_OK;
+}
+
+int rb_learner_get_horizon(rb_learner_t* l, int32_t* n_eff, double* discount) {
+  RB_REQUIRE(l && n_eff && discount, "rb_learner_get_horizon: NULL argument");
+  *n_eff = l->n_eff; *discount = l->discount;
+  return RB_OK;
+}
+
 int rb_learner_set_step_counter(rb_learner_t* l, int64_t* step_dev) {
   RB_REQUIRE(l != nullptr, "rb_learner_set_step_counter: NULL handle");
   l->step_ctr = reinterpret_cast<long long*>(step_dev);

@@ -265,7 +265,9 @@ struct rb_learner {
   float* noise_snap;        // [n_noise] the online noise of the learn call in flight, copied by its last backward launch
   int32_t* status_copy;     // this learn call's batch_status, copied by its head kernel: the hosted pass shares a launch with
                             // the NEXT call's sampler, which overwrites the replay header's word
-  float gamma_n;        // float32(discount ** n)        agent.py:79
+  float gamma_n;        // float32(discount ** n)        agent.py:79  (n and discount: the two below)
+  int32_t n_eff;        // the effective horizon (rb_learner_set_horizon; cfg.multi_step until then): the next-state slot of the window
+  double discount;      // table (SrcDesc n_step) and the exponent of gamma_n — host state, read when a step is launched
   float delta_z;        // float32((Vmax - Vmin)/(Z-1))   agent.py:19,82
 };
 

@@ -31,7 +31,9 @@
 // ---------------------------------------------------------------------- handle --
 struct rb_replay {
   int64_t capacity;
-  int32_t history, n;
+  int32_t history, n;   // n = n_max, the multi_step of creation: every allocation, the window table's row stride history + n
+  int32_t n_eff;        // the effective horizon, 1 <= n_eff <= n (rb_replay_set_horizon; n until then)
+  double discount;      // the discount scaling[] was last filled from
   int32_t levels;       // L = depth of the leaf level
   int32_t streams;      // S interleaved environment streams (1 = the reference's single sequential stream)
   int64_t tree_start;   // 2^L - 1
@@ -90,7 +92,7 @@ static int spec_join(rb_replay* r) {
 
 static ReplayView view_of(const rb_replay* r) {
   ReplayView v;
-  v.capacity = r->capacity; v.history = r->history; v.n = r->n; v.levels = r->levels; v.streams = r->streams;
+  v.capacity = r->capacity; v.history = r->history; v.n = r->n_eff; v.levels = r->levels; v.streams = r->streams;
   v.tree_start = r->tree_start; v.tree_len = r->tree_len;
   v.tree = r->tree; v.frames = r->frames; v.timestep = r->timestep; v.action = r->action;
   v.reward = r->reward; v.nonterminal = r->nonterminal; v.hdr = r->hdr;
@@ -122,6 +124,7 @@ void rb_replay_note_device_write(void* dst_dev, const void* src_host, size_t nby
 int rb_replay_spec_inflight(rb_replay_t* r) { return r ? r->spec_inflight : 0; }
 const int32_t* rb_replay_current_windows(rb_replay_t* r) { return win_of(r, r->win_sel); }
 unsigned long long rb_replay_mutations(rb_replay_t* r) { return r->mutations; }
+void rb_replay_horizon(rb_replay_t* r, int32_t* n_eff, double* discount) { *n_eff = r->n_eff; *discount = r->discount; }
 
 // (replay_internal.h) the write-back of learn call k + the tentative draw of call k + 1 on the replay's own stream
 int rb_replay_spec_allowed(rb_replay_t* r) {
@@ -185,6 +188,14 @@ __global__ void k_replay_init(rb_replay_header_t* hdr) {
   }
 }
 
+// gamma^k for rb_replay_set_horizon: the table travels BY VALUE in the kernel arguments and is stored in stream order — a sampler
+// launch queued before this one reads the old table, the next one the new, with no copy from pageable memory and no synchronisation
+struct HorizonTable { float s[64]; };
+__global__ __launch_bounds__(64) void k_set_horizon(float* scaling, HorizonTable tab) {
+  const int t = (int)threadIdx.x;
+  if (blockIdx.x == 0 && t < 64) scaling[t] = tab.s[t];
+}
+
 extern "C" {
 
 static int create_impl(rb_replay_t** out, int64_t capacity, int32_t history, int32_t multi_step, double discount,
@@ -198,13 +209,14 @@ static int create_impl(rb_replay_t** out, int64_t capacity, int32_t history, int
   rb_replay* r = new (std::nothrow) rb_replay();
   if (!r) { rb_set_error("rb_replay_create: host OOM"); return RB_ERR_OOM; }
   r->capacity = capacity; r->history = history; r->n = multi_step; r->omega = priority_exponent; r->seed = seed;
-  r->streams = streams;
+  r->streams = streams; r->n_eff = multi_step; r->discount = discount;
   int32_t L = 0;
   while (((int64_t)1 << L) < capacity) ++L;  // (capacity-1).bit_length()   memory.py:17
   r->levels = L;
   r->tree_start = ((int64_t)1 << L) - 1;
   r->tree_len = r->tree_start + capacity;
   for (int k = 0; k < multi_step; ++k) r->scaling[k] = (float)pow(discount, (double)k);  // memory.py:101
+  { const int32_t stride = history + multi_step; memcpy(&r->scaling[RB_STRIDE_SLOT], &stride, sizeof(stride)); }   // replay_internal.h
   r->max_batch = 1024;            // (every other field stays as rb_replay() value-initialised it: null, 0)
 #define RB_ALLOC(ptr, bytes)                                                                      \
   do {                                                                                            \
@@ -430,6 +442,33 @@ int rb_replay_set_beta_source(rb_replay_t* r, const float* neg_beta_dev) {
   return RB_OK;
 }
 
+// The effective horizon and the discount of a live replay (include/rainbow_hip.h): from the next draw on the batch is the one a
+// replay created with multi_step = n_eff and this discount draws from the same ring, tree and uniforms.  Allocations, the row stride
+// of the window table (history + the multi_step of creation) and rb_replay_buffers_t.window_len do not change.
+int rb_replay_set_horizon(rb_replay_t* r, int32_t n_eff, double discount, rb_stream_t stream) {
+  RB_REQUIRE(r != nullptr, "rb_replay_set_horizon: NULL handle");
+  RB_REQUIRE(n_eff >= 1 && n_eff <= r->n, "rb_replay_set_horizon: n_eff must be in [1, %d] (the multi_step the replay was created "
+             "with), got %d", (int)r->n, (int)n_eff);
+  RB_REQUIRE(discount > 0.0 && discount <= 1.0, "rb_replay_set_horizon: discount must be in (0, 1], got %g", discount);   // (also NaN)
+  RB_SPEC_JOIN(r);                // a tentative early draw made under the old horizon is never accepted
+  ++r->mutations;
+  HorizonTable tab;
+  memset(&tab, 0, sizeof(tab));
+  for (int k = 0; k < r->n; ++k) tab.s[k] = (float)pow(discount, (double)k);  // memory.py:101, as create_impl
+  tab.s[RB_STRIDE_SLOT] = r->scaling[RB_STRIDE_SLOT];                         // the row stride stays (its bits, not a float value)
+  RB_LAUNCH(k_set_horizon, dim3(1), dim3(64), stream, r->scaling_dev, tab);
+  RB_LAUNCH_CHECK();
+  memcpy(r->scaling, tab.s, sizeof(tab.s));
+  r->n_eff = n_eff; r->discount = discount;
+  return RB_OK;
+}
+
+int rb_replay_get_horizon(rb_replay_t* r, int32_t* n_eff, double* discount) {
+  RB_REQUIRE(r && n_eff && discount, "rb_replay_get_horizon: NULL argument");
+  *n_eff = r->n_eff; *discount = r->discount;
+  return RB_OK;
+}
+
 int rb_replay_find(rb_replay_t* r, const double* values_dev, int32_t n, float* probs_dev, int64_t* data_idx_dev,
                    int64_t* tree_idx_dev, rb_stream_t stream) {
   RB_REQUIRE(r && values_dev && probs_dev && data_idx_dev && tree_idx_dev, "rb_replay_find: NULL argument");
@@ -442,10 +481,10 @@ int rb_replay_find(rb_replay_t* r, const double* values_dev, int32_t n, float* p
 }
 
 // the frame stacks of a drawn batch, where the caller wants them (NULL: the learner reads the ring through the window table)
-static int launch_gather(const ReplayView& v, int32_t batch, const int32_t* win, uint8_t* states_dev, uint8_t* next_states_dev,
-                         rb_stream_t stream) {
+static int launch_gather(const ReplayView& v, int32_t win_stride, int32_t batch, const int32_t* win, uint8_t* states_dev,
+                         uint8_t* next_states_dev, rb_stream_t stream) {
   if (!states_dev || !next_states_dev) return RB_OK;
-  RB_LAUNCH(k_gather_stacks, dim3((unsigned)(batch * 2 * v.history)), dim3(256), stream, v, batch, win, states_dev, next_states_dev);
+  RB_LAUNCH(k_gather_stacks, dim3((unsigned)(batch * 2 * v.history)), dim3(256), stream, v, batch, win, win_stride, states_dev, next_states_dev);
   RB_LAUNCH_CHECK();
   return RB_OK;
 }
@@ -535,7 +574,7 @@ static int sample_impl(rb_replay_t* r, int32_t batch, double priority_weight, co
   else if (wide) launch(k_sample<1024, RB_HOST_AU_WIDE>);
   else launch(k_sample<256, 8>);
   RB_LAUNCH_CHECK();
-  return launch_gather(v, batch, win_cur, states_dev, next_states_dev, stream);
+  return launch_gather(v, r->history + r->n, batch, win_cur, states_dev, next_states_dev, stream);
 }
 
 int rb_replay_sample(rb_replay_t* r, int32_t batch, double priority_weight, const double* unit_uniforms_dev,
@@ -605,7 +644,7 @@ int rb_replay_update_sample(rb_replay_t* r, const int64_t* upd_tree_idx_dev, con
               batch, neg_beta, r->neg_beta_dev, unit_uniforms_dev, max_attempts, r->seed, r->scaling_dev, tree_idx_dev, r->win, actions_dev,
               returns_dev, nonterminals_dev, weights_dev, r->fail_host, (SpecResult*)nullptr, 0u);
   RB_LAUNCH_CHECK();
-  return launch_gather(v, batch, r->win, states_dev, next_states_dev, stream);
+  return launch_gather(v, r->history + r->n, batch, r->win, states_dev, next_states_dev, stream);
 }
 
 // The frame stacks of the LAST draw on the handle with random-shift augmentation (replay_shift.h): reads the window table that draw
@@ -622,7 +661,7 @@ int rb_replay_gather_shifted(rb_replay_t* r, int32_t batch, int32_t pad, uint64_
              "rb_replay_gather_shifted: states_dev and next_states_dev must be 16-byte aligned");
   RB_SPEC_JOIN(r);
   RB_LAUNCH_T("sample:k_gather_stacks_shift", k_gather_stacks_shift, dim3((unsigned)(batch * 2 * r->history)), dim3(256), stream, view_of(r),
-              batch, win_of(r, r->win_sel), pad, r->seed ^ RB_SHIFT_KEY_TAG, draw, shifts_in_dev, states_dev, next_states_dev,
+              batch, win_of(r, r->win_sel), r->history + r->n, pad, r->seed ^ RB_SHIFT_KEY_TAG, draw, shifts_in_dev, states_dev, next_states_dev,
               shifts_out_dev);
   RB_LAUNCH_CHECK();
   return RB_OK;

@@ -7,7 +7,10 @@
 
 struct ReplayView {
   int64_t capacity;
-  int32_t history, n, levels;
+  int32_t history, n, levels;   // n: the EFFECTIVE horizon (rb_replay_set_horizon), 1 <= n <= the multi_step of creation.  The row
+                        // stride of the window table, history + the multi_step of creation, is NOT in the view: any change of this
+                        // struct's layout slowed the data-efficient step by ~1 us (profiles/horizon_bench.txt); the samplers read it
+                        // from word RB_STRIDE_SLOT of the gamma^k table, the gathers take it as an argument
   int32_t streams;      // S interleaved environment streams (rb_replay_create_streams): stream s owns the slots s, s + S, s + 2S, ...
                         // (fills what was the padding in front of tree_start: the view keeps its size)
   int64_t tree_start, tree_len;
@@ -35,6 +38,8 @@ __device__ __forceinline__ int64_t rb_floor_mod(int64_t a, int64_t m) {
   return r < 0 ? r + m : r;
 }
 
+#define RB_STRIDE_SLOT 63     // word of the 64-word gamma^k table that holds the window table's row stride as an int32 (history + multi_step
+                             // <= 64 and history >= 1, so gamma^63 is never needed)
 #define RB_MAX_LEVELS 31     // deepest tree (capacity <= 2^30, rb_replay_create)
 
 #include "replay_update.h"
@@ -61,3 +66,6 @@ int rb_replay_spec_inflight(rb_replay_t* r);
 // the window table the LAST draw on the handle filled (rb_replay_buffers_t.window_dev is table 0; an accepted early draw used the other)
 const int32_t* rb_replay_current_windows(rb_replay_t* r);
 unsigned long long rb_replay_mutations(rb_replay_t* r);
+// the effective horizon and discount of the handle (rb_replay_set_horizon), host values: what rb_learner_train_step compares with the
+// learner's own before it draws
+void rb_replay_horizon(rb_replay_t* r, int32_t* n_eff, double* discount);

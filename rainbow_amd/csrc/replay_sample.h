@@ -7,10 +7,13 @@
 
 // Window, scalars and importance weight of ONE sample (memory.py:111-121,140-145,151-153) with every load of the window
 // requested in a single batch: NCH chunks of 8 timesteps and 8 rewards (NCH = ceil((h + n) / 8): 1 for n = 3, 3 for the
-// data-efficient n = 20 — whose second and third chunk used to be two more dependent round trips each).
+// data-efficient n = 20 — whose second and third chunk used to be two more dependent round trips each).  n is the EFFECTIVE horizon
+// v.n: the return, the nonterminal slot, the next-state slots and the blanking are those of a replay built with multi_step = n; the
+// row of the window table keeps the stride history + n_max — word RB_STRIDE_SLOT of `scaling`, a load in the window's own batch —
+// and its slots from h + n on are -1, never a ring index.
 template <int NCH>
 __device__ __forceinline__ float rb_sample_window(const ReplayView& v, int64_t idx, float prob, float p_total, int32_t full,
-                                                  int64_t w_index, float neg_beta_f32, const float* scaling, int32_t* my_win,
+                                                  int64_t w_index, float neg_beta_f32, const float* scaling, int32_t* win,
                                                   int64_t* action_out, float* return_out, float* nonterminal_out) {
   // ring slots as 32-bit, wrapped with two selects (capacity > window, checked by the host; |offset| < capacity): the
   // 64-bit while-loop form put control flow between the loads, and every load became its own ~0.35 us round trip
@@ -22,6 +25,7 @@ __device__ __forceinline__ float rb_sample_window(const ReplayView& v, int64_t i
   const int32_t id = (int32_t)idx;
   const int h = v.history, n = v.n;
   const int win_len = h + n;
+  int32_t win_stride = reinterpret_cast<const int32_t*>(scaling)[RB_STRIDE_SLOT];
   auto wrap = [C](int32_t x) { x += x < 0 ? C : 0; x -= x >= C ? C : 0; return x; };
   const int32_t first = id - (h - 1) * S;                             // window slot 0 (unwrapped)
   constexpr int NT = 8 * NCH;
@@ -60,7 +64,14 @@ __device__ __forceinline__ float rb_sample_window(const ReplayView& v, int64_t i
     const bool b = ((blank >> (t - 1)) & 1ull) || ((first_bits >> t) & 1ull);
     if (b) blank |= 1ull << t;
   }
+  // (the stride was requested in front of the window's loads and is first USED here, next to the stores that need it: the
+  // empty statement keeps the row address from being formed, and the load from being waited for, in the middle of the batch)
+#if !defined(RB_HOST_INTERP)
+  asm volatile("" : "+v"(win_stride));
+#endif
+  int32_t* my_win = win + (int64_t)threadIdx.x * win_stride;            // thread i = sample i
   for (int t = 0; t < win_len; ++t) my_win[t] = ((blank >> t) & 1ull) ? -1 : wrap(first + t * S);
+  for (int t = win_len; t < win_stride; ++t) my_win[t] = -1;          // the row's tail: -1 like a blanked slot, never a ring index
   *action_out = (int64_t)act_now;                                     // memory.py:140
   float R = 0.0f;                                                     // memory.py:142-143, k ascending
 #pragma unroll
@@ -168,10 +179,9 @@ __device__ __forceinline__ void rb_sample_main(const ReplayView& v, int32_t batc
   if (active) {
     const int64_t idx = leaf - v.tree_start;
     const int win_len = h + n;
-    int32_t* my_win = win + (int64_t)i * win_len;
     float nt_f;
-    const int nch = (win_len + 7) >> 3;                                 // block-uniform
-#define RB_WIN(N) w = rb_sample_window<N>(v, idx, prob, p_total, full, w_index, neg_beta_f32, scaling, my_win, &actions_out[i], &returns_out[i], &nt_f)
+    const int nch = (win_len + 7) >> 3;                                 // block-uniform (of the effective window, not the stride)
+#define RB_WIN(N) w = rb_sample_window<N>(v, idx, prob, p_total, full, w_index, neg_beta_f32, scaling, win, &actions_out[i], &returns_out[i], &nt_f)
     if (nch <= 1) RB_WIN(1);
     else if (nch <= 3 || MAXT > 256) RB_WIN(3);      // (the 1024-thread variant has no registers for longer windows in one batch ...
     else RB_WIN(8);                                  //  ... rb_replay_sample refuses batch > 256 with history + multi_step > 24)
@@ -279,7 +289,7 @@ __global__ __launch_bounds__(MAXT) void k_sample(ReplayView v, int32_t batch, fl
 // 441 sixteen-byte lanes per 7056-byte frame, zero fill for blanked slots.
 // Stream-agnostic: the ring slot of every frame comes from the sampler's window table, which already holds the stream's
 // stride (rb_sample_window); the learner's zero-copy conv path reads the ring through the same table.
-__global__ __launch_bounds__(256) void k_gather_stacks(ReplayView v, int32_t batch, const int32_t* win,
+__global__ __launch_bounds__(256) void k_gather_stacks(ReplayView v, int32_t batch, const int32_t* win, int32_t win_stride,
                                                         uint8_t* states, uint8_t* next_states) {
   constexpr int VEC = RB_FRAME_BYTES / 16;
   const int h = v.history, n = v.n;
@@ -290,7 +300,7 @@ __global__ __launch_bounds__(256) void k_gather_stacks(ReplayView v, int32_t bat
     const bool is_next = s >= h;
     const int c = is_next ? s - h : s;
     const int slot = is_next ? n + c : c;
-    const int32_t ring = win[(int64_t)i * (h + n) + slot];
+    const int32_t ring = win[(int64_t)i * win_stride + slot];
     uint4* d = (uint4*)((is_next ? next_states : states) + ((int64_t)i * h + c) * RB_FRAME_BYTES);
     if (ring < 0) {
       const uint4 z = make_uint4(0u, 0u, 0u, 0u);

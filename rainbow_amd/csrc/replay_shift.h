@@ -25,7 +25,7 @@ __device__ __forceinline__ int rb_shift_from_u32(uint32_t v, int pad) {
 // (dy, dx) is shared by the `history` frames of one (i, w): injected (shifts_in, int8 [B][2][2] = [i][w] -> (dy, dx), clamped to
 // [-pad, pad]) or Philox4x32-10 with key seed ^ RB_SHIFT_KEY_TAG and counter (hi = draw, lo = i): words 0, 1 = the state's
 // (dy, dx), words 2, 3 = the next state's.  The header (its rng_counter included) is not touched.
-__global__ __launch_bounds__(256) void k_gather_stacks_shift(ReplayView v, int32_t batch, const int32_t* win, int32_t pad,
+__global__ __launch_bounds__(256) void k_gather_stacks_shift(ReplayView v, int32_t batch, const int32_t* win, int32_t win_stride, int32_t pad,
                                                               uint64_t key, uint64_t draw, const int8_t* shifts_in,
                                                               uint8_t* states, uint8_t* next_states, int8_t* shifts_out) {
   constexpr int VEC = RB_FRAME_BYTES / 16;
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_gather_stacks_shift(ReplayView v, int32
     shifts_out[(i * 2 + w) * 2 + 0] = (int8_t)dy;
     shifts_out[(i * 2 + w) * 2 + 1] = (int8_t)dx;
   }
-  const int32_t ring = win[(int64_t)i * (h + n) + slot];
+  const int32_t ring = win[(int64_t)i * win_stride + slot];
   uint4* d = (uint4*)((w ? next_states : states) + ((int64_t)i * h + c) * RB_FRAME_BYTES);
   if (ring < 0) {                                                      // block-uniform: a blanked slot stays blank
     const uint4 z = make_uint4(0u, 0u, 0u, 0u);

@@ -12,6 +12,7 @@ their u8 screens into the front end's pinned staging, one upload and one launch 
 
 `evaluate_vec` / `evaluate_host_vec` are the reference's evaluation (test.py:13-41) for the same two kinds of environment:
 epsilon-greedy actions drawn in the batched act path, the per-episode list of returns, `episodes` spread evenly over the streams."""
+import math
 from contextlib import contextmanager
 
 import numpy as np
@@ -20,15 +21,50 @@ import torch
 from .evaluate import EpisodeTally, stream_quotas
 
 
+def horizon_at(t, n0, n1, g0, g1, T):
+    """BBF's annealed update horizon and discount, a pure function: t gradient steps after the last reset (or the start) the
+    horizon has moved geometrically from n0 towards n1 and 1 - gamma geometrically from 1 - g0 towards 1 - g1, both reaching their
+    end at t = T and staying there.  With f = min(t, T) / T:  n = floor(n0 * (n1 / n0) ** f + 0.5),
+    gamma = 1 - (1 - g0) * ((1 - g1) / (1 - g0)) ** f.  (BBF: 10 -> 3 and 0.97 -> 0.997 over T = 10 000.)  Returns (n, gamma)."""
+    f = (min(t, T) / T) if T > 0 else 1.0
+    n = int(math.floor(n0 * (n1 / n0) ** f + 0.5))
+    if g1 == g0:
+        return n, float(g0)                                                       # (no rounding of 1 - (1 - g0))
+    if not (g0 < 1 and g1 < 1):
+        raise ValueError("horizon_at: 1 - gamma is interpolated geometrically, so both discounts must be below 1")
+    return n, 1 - (1 - g0) * ((1 - g1) / (1 - g0)) ** f
+
+
 def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states, round_fn):
     """The cadence of main.py:146-184 at S environment steps per round, shared by train_device and train_host_vec:
-    round_fn(states) acts, steps the environment and appends the round to `mem`, and returns the next states."""
+    round_fn(states) acts, steps the environment and appends the round to `mem`, and returns the next states.
+    args.multi_step_final (absent: no schedule, set_horizon is never called) anneals the horizon from args.multi_step and, with
+    args.discount_final, the discount from args.discount (horizon_at) over args.horizon_anneal_steps (10 000) gradient steps counted
+    from the start or the last reset: agent and memory are set before the first learn step, before every learn step whose count t is
+    a multiple of args.horizon_update_interval (100) up to the end of the anneal, at t = horizon_anneal_steps, and right after each
+    agent.reset_parameters(), which restarts t at 0."""
     seed = int(getattr(args, "seed", 0))
     increase = (1 - args.priority_weight) / (T_max - args.learn_start)           # main.py:123
     eval_every = int(getattr(args, "evaluation_interval", 0) or 0)
     replay_ratio = float(getattr(args, "replay_ratio", 0) or 0)                   # learn steps per environment step; may exceed 1
     reset_interval = int(getattr(args, "reset_interval", 0) or 0)                 # in GRADIENT steps; 0 = never
     learn_owed, learns = 0.0, 0
+    n1 = getattr(args, "multi_step_final", None)
+    set_horizon = None
+    if n1 is not None:
+        n0, n1, g0 = int(args.multi_step), int(n1), float(args.discount)
+        if n1 > n0:
+            raise ValueError("multi_step_final (%d) must not exceed multi_step (%d): the horizon anneals downwards" % (n1, n0))
+        g1 = getattr(args, "discount_final", None)
+        g1 = g0 if g1 is None else float(g1)
+        anneal = int(getattr(args, "horizon_anneal_steps", 10000))
+        interval = max(1, int(getattr(args, "horizon_update_interval", 100)))
+
+        def set_horizon(t):
+            n, g = horizon_at(t, n0, n1, g0, g1, anneal)
+            agent.set_horizon(n, g)
+            mem.set_horizon(n, g)
+    since_reset, horizon_set_at = 0, None         # gradient steps since the last reset; the count the horizon was last set for
     if per_stream_noise:
         agent.reset_noise_rows(S, rng=(seed, 0))                                  # S < replay_frequency: the first rounds come before the first redraw
     for T in range(1, T_max + 1, S):
@@ -41,11 +77,20 @@ def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states,
             mem.priority_weight = min(mem.priority_weight + increase * S, 1)      # main.py:161
             learn_owed += S * replay_ratio if replay_ratio > 0 else S / args.replay_frequency
             while learn_owed >= 1:
+                if (set_horizon is not None and since_reset != horizon_set_at and since_reset <= anneal
+                        and (since_reset % interval == 0 or since_reset == anneal)):
+                    set_horizon(since_reset)
+                    horizon_set_at = since_reset
                 agent.learn(mem)                                                  # main.py:164
                 learn_owed -= 1
                 learns += 1
+                since_reset += 1
                 if reset_interval and learns % reset_interval == 0:
                     agent.reset_parameters()                                      # shrink-and-perturb (Agent.reset_parameters)
+                    since_reset = 0
+                    if set_horizon is not None:
+                        set_horizon(0)                                            # the anneal starts again with the reset
+                        horizon_set_at = 0
             if on_eval is not None and eval_every and T % eval_every < S:         # main.py:166-170
                 on_eval(T)
                 agent.train()
@@ -64,6 +109,9 @@ def train_device(agent, mem, env, args, T_max, on_eval=None, per_stream_noise=Fa
     1 — S * replay_ratio learn steps are owed per round.  args.reset_interval (absent or 0: never) counts GRADIENT steps: right
     after the learn() that makes the count a multiple of it, agent.reset_parameters() shrinks and perturbs the networks
     (args.reset_shrink_encoder / reset_shrink_head) — what keeps a replay ratio above 1 from hurting.
+    args.multi_step_final (absent: no schedule, no set_horizon call ever) anneals the update horizon from args.multi_step and,
+    with args.discount_final, the discount from args.discount after the start and after every reset (horizon_at, _train_rounds;
+    args.horizon_anneal_steps, args.horizon_update_interval): agent.set_horizon and mem.set_horizon, INTEGRATION.md §2.
     on_eval(T), if given, is called at the evaluation rounds (args.evaluation_interval); it may synchronise.
     per_stream_noise=True: every stream acts under its OWN noisy-net sample — agent.reset_noise_rows(S, rng=(args.seed, T)) at
     the cadence of reset_noise() (which stays: learn() needs the learner's own sample) and act_batch(per_row_noise=True);
@@ -110,7 +158,7 @@ def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None, per_strea
     Cadences are train_device's: reset_noise once per replay_frequency env steps; from learn_start on, beta annealed by
     priority_weight_increase * S per round, one learn() per replay_frequency env steps (learn_owed) — or S * args.replay_ratio
     per round, with agent.reset_parameters() every args.reset_interval gradient steps, as in train_device — target update and
-    on_eval at `T % k < S`.  per_stream_noise: as in train_device (one noise sample per emulator).  Returns the number of learn() calls made."""
+    on_eval at `T % k < S`; args.multi_step_final and its companions anneal the horizon as in train_device.  per_stream_noise: as in train_device (one noise sample per emulator).  Returns the number of learn() calls made."""
     S = len(emus)
     if S != mem.streams or S != front.streams:
         raise ValueError("train_host_vec: %d emulators, a front end of %d streams, a memory of %d" % (S, front.streams, mem.streams))

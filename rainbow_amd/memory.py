@@ -21,6 +21,10 @@ stack by (dy, dx) in [-p, p] with edge replication — `states` and `next_states
 alike — inside the frame-stack gather (rb_replay_gather_shifted).  Only `sample_device(gather=True)` and `sample()` are shifted;
 `__next__`, `state_at` / `states_at` (validation, evaluation) never are.
 
+Annealed update horizon and discount (BBF): `set_horizon(n, discount=None)` changes the effective multi-step horizon (1 <= n <= the
+`multi_step` of construction, which `.n` keeps naming) and the discount of the LIVE replay, ring and tree untouched; `.horizon` and
+`.discount` are the values in force.  The next batch is the one a replay built with multi_step = n would draw.
+
 This module: construction, sampling and priorities.  The write side (append and its per-stream forms) is memory_append.py; the
 column table, save_to / load_from and pickling are memory_state.py.
 """
@@ -88,6 +92,7 @@ class ReplayMemory(ReplayAppend, ReplayState):
     streams = 1                 # (a pickle written before interleaved streams existed restores as one stream)
     augment_pad = 0             # (a pickle written before the random-shift option existed restores with it off)
     _aug_draw = 0               # batches shifted so far: the `draw` word of the shift RNG's counter (rb_replay_gather_shifted)
+    horizon = None              # (a pickle written before set_horizon existed restores at horizon == n: __setstate__)
     MAX_AUGMENT_PAD = 8
     _lazy = os.environ.get("RAINBOW_AMD_LAZY_PRIORITIES", "1") != "0"
 
@@ -116,7 +121,8 @@ class ReplayMemory(ReplayAppend, ReplayState):
         self.capacity = int(capacity)
         self.history = int(args.history_length)
         self.discount = float(args.discount)
-        self.n = int(args.multi_step)
+        self.n = int(args.multi_step)                           # n_max: allocations and the window table's row stride
+        self.horizon = self.n                                   # the effective horizon (set_horizon; learn() reads it every step)
         self.priority_weight = float(args.priority_weight)      # beta, annealed by the caller (main.py:161)
         self.priority_exponent = float(args.priority_exponent)
         self.t = 0                                              # episode timestep counter (memory.py:100)
@@ -172,6 +178,22 @@ class ReplayMemory(ReplayAppend, ReplayState):
                 rc = self._lib.rb_replay_create_streams(C.byref(self._h), self.capacity, self.history, self.n, self.discount,
                                                         self.priority_exponent, self._seed, self.streams)
             L.check(self._lib, rc)
+            if self.horizon != self.n:      # (a restored state: the handle is created at n_max and the discount in force)
+                L.check(self._lib, self._lib.rb_replay_set_horizon(self._handle, self.horizon, self.discount, self._stream()))
+
+    def set_horizon(self, n, discount=None):
+        """The effective horizon and discount of the live replay (rb_replay_set_horizon): 1 <= n <= self.n, 0 < discount <= 1,
+        None keeps the current discount.  A pending lazy write-back is applied first; one tiny launch in stream order, no
+        synchronisation.  The learner that consumes the batches must be set to the same pair (Agent.set_horizon): Agent.learn
+        compares and raises."""
+        n = int(n)
+        g = float(self.discount if discount is None else discount)
+        if not 1 <= n <= self.n:
+            raise ValueError("set_horizon: n must be in [1, %d] (the multi_step of construction), got %d" % (self.n, n))
+        if not 0.0 < g <= 1.0:                                  # (also NaN)
+            raise ValueError("set_horizon: discount must be in (0, 1], got %r" % g)
+        L.check(self._lib, self._lib.rb_replay_set_horizon(self._h, n, g, self._stream()))
+        self.horizon, self.discount = n, g
 
     def _init_beta_source(self):
         # -beta lives in HBM so a captured hipGraph sees main.py:161's annealing (by-value kernel arguments freeze)

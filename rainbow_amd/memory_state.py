@@ -49,7 +49,7 @@ class ReplayState:
         hdr = self._header()
         self.stream_t             # (fetches the device-resident counters after device rounds; refreshes self.t)
         meta = dict(version=1, capacity=self.capacity, history=self.history, n=self.n, discount=self.discount,
-                    priority_weight=self.priority_weight, priority_exponent=self.priority_exponent, t=self.t,
+                    horizon=int(self.horizon), priority_weight=self.priority_weight, priority_exponent=self.priority_exponent, t=self.t,
                     streams=self.streams, stream_t=[int(x) for x in self.stream_t], seed=self._seed,
                     augment_pad=int(self.augment_pad), aug_draw=int(self._aug_draw),
                     columns={k: rows * row for k, (_p, row, _d, rows) in cols.items()}, header=bytes(hdr).hex())
@@ -77,6 +77,9 @@ class ReplayState:
                                      augment_pad=meta.get("augment_pad", 0))                  # (older streams: no augmentation)
         mem = cls(args, meta["capacity"], seed=meta["seed"], streams=meta.get("streams", 1))   # (older streams: one stream)
         mem._aug_draw = int(meta.get("aug_draw", 0))
+        horizon = int(meta.get("horizon", meta["n"]))            # (older streams: the horizon of construction)
+        if horizon != mem.n:
+            mem.set_horizon(horizon)                             # (meta["discount"] is the discount that was in force)
         mem.t = meta["t"]
         mem.stream_t = np.array(meta.get("stream_t", [meta["t"]]), dtype=np.int32)
         b, cols = mem._columns()
@@ -124,6 +127,8 @@ class ReplayState:
         self.__dict__.update(st)
         self.augment_pad = self._checked_pad(st.get("augment_pad", 0))      # (a pickle from before the option: off, draw 0)
         self._aug_draw = int(st.get("_aug_draw", 0))
+        if self.horizon is None:                                             # (a pickle from before set_horizon: the horizon of construction)
+            self.horizon = self.n
         self.device = torch.device(self.device)
         # (a pickle from before interleaved streams: one stream)
         self.stream_t = np.array([self.t], dtype=np.int32) if stream_t is None else np.asarray(stream_t, dtype=np.int32)
