@@ -72,7 +72,10 @@ int rb_profile_overhead(rb_stream_t stream, int32_t n, double* mean_ms);
 /* Test hook (no reference counterpart).  With RB_GUARD=1 in the environment when the library is loaded, every device
  * allocation the library owns (replay ring, sum-tree, learner workspaces) sits between two 4 KiB guard bands; this call
  * synchronises the device and reports how many blocks are live and how many have a band that a kernel wrote into
- * (tests/test_guard_gpu.py).  Without RB_GUARD it reports 0 / 0.                                                     */
+ * (tests/test_guard.py).  Under RB_GUARD=1 the block between the bands is zeroed; RB_GUARD=2 is the same in every other
+ * respect but leaves the block at the bands' fill byte 0xC5 (as f32 a finite -6.3e3, as an integer nonsense), so that a
+ * kernel reading memory nobody has written changes its result: the same run under 1 and under 2 must give bit-identical
+ * outputs (tests/test_poison_emu.py, tests/test_poison_gpu.py).  Without RB_GUARD it reports 0 / 0.                  */
 int rb_debug_check_guards(int64_t* n_blocks, int64_t* n_bad);
 
 /* ===================================================================== replay ==
@@ -510,6 +513,12 @@ int rb_learner_noise_layout(const rb_learner_config_t* cfg, rb_tensor_desc_t* de
 int rb_debug_launch_plan(const rb_learner_config_t* cfg, const char* rb_opts, int32_t n_cu, int32_t flags, int32_t world,
                          int32_t with_sink, char* out, int64_t cap);
 
+/* The five buffers are caller-owned flat f32 buffers of rb_learner_sizes floats (n_params: both parameter buffers and grads_dev;
+ * n_noise: both noise buffers) and must outlive the handle.  grads_dev is ZERO-FILLED by this call: a learn call writes the
+ * tensors' elements only, while the gradient norm of the fallback / all-reduce route (one sum of squares over the whole flat
+ * buffer) and the optimiser pass sweep the alignment padding between the tensors as well — it must stay zero, so a caller that
+ * overwrites grads_dev (an all-reduce, rb_learner_grads_modified) keeps zeros there.  The same padding of the parameter buffers
+ * and of the Adam moments is updated with that zero gradient and is never read into a result.                                 */
 int rb_learner_create(rb_learner_t** out, const rb_learner_config_t* cfg, float* online_params_dev,
                       float* target_params_dev, float* grads_dev, float* online_noise_dev,
                       float* target_noise_dev, uint64_t seed);

@@ -85,10 +85,18 @@ extern "C" int rb_debug_host_timing(int reset) {
 #define RB_GUARD_FILL 0xC5
 struct GuardedBlock { char* raw; char* user; size_t bytes; };
 static std::vector<GuardedBlock> g_guarded;
-static int guard_on() {
-  static const int on = getenv("RB_GUARD") && getenv("RB_GUARD")[0] == '1';
-  return on;
+// RB_GUARD=1: guard bands, user block zeroed.  RB_GUARD=2: the same bands, and the user block is left at RB_GUARD_FILL too, so a
+// kernel that reads memory nobody wrote sees poison, not the zero a fresh page happens to hold.  0xC5 on purpose: as f32 the word
+// 0xC5C5C5C5 is a finite -6.3e3 (a staged pad lane that meets a zero weight or is masked at the store stays harmless — no NaN
+// false positives — while anything that really enters a result moves it visibly); as an integer it is large and nonsensical.
+static int guard_level() {
+  static const int level = [] {
+    const char* e = getenv("RB_GUARD");
+    return e && (e[0] == '1' || e[0] == '2') ? e[0] - '0' : 0;
+  }();
+  return level;
 }
+static int guard_on() { return guard_level() != 0; }
 hipError_t rb_dev_malloc(void** p, size_t bytes) {
   if (!guard_on()) return hipMalloc(p, bytes);
   const size_t padded = (bytes + 255) / 256 * 256;             // keep the user block's end 256-byte aligned like its start
@@ -97,7 +105,7 @@ hipError_t rb_dev_malloc(void** p, size_t bytes) {
   if (e != hipSuccess) return e;
   e = hipMemset(raw, RB_GUARD_FILL, padded + 2 * RB_GUARD_BYTES);   // guards AND the alignment tail [bytes, padded)
   if (e != hipSuccess) { (void)hipFree(raw); return e; }
-  if (bytes) {
+  if (bytes && guard_level() == 1) {
     e = hipMemset(raw + RB_GUARD_BYTES, 0, bytes);
     if (e != hipSuccess) { (void)hipFree(raw); return e; }
   }

@@ -267,6 +267,9 @@ int rb_learner_create(rb_learner_t** out, const rb_learner_config_t* cfg, float*
   RB_HIP_TRY(hipMemcpy(l->support, sup, L.Z * sizeof(float), hipMemcpyHostToDevice));
   RB_HIP_TRY(hipMemset(l->zero_noise, 0, L.n_noise * sizeof(float)));
   RB_HIP_TRY(hipMemset(l->hpart, 0, (size_t)l->caps.hs * NI * 2 * L.H * 4));
+  // the learn call writes the tensors' elements only; k_sumsq (sumsq_pass) and the optimiser pass sweep the whole flat buffer, the
+  // alignment padding between the tensors included: it is cleared here, once, and stays zero (include/rainbow_hip.h)
+  RB_HIP_TRY(hipMemset(grads_dev, 0, (size_t)L.n_params * 4));
   {
     const int rc = upload_noise_jobs(l);
     if (rc != RB_OK) return rc;

@@ -36,8 +36,9 @@ void rb_set_error(const char* fmt, ...);
   } while (0)
 
 // ---- device allocations of the library (workspaces, the replay ring) ---------------
-// hipMalloc / hipFree, except under RB_GUARD=1 (test runs): every block is then surrounded by two 4 KiB guard bands filled
-// with a fixed byte, and rb_debug_check_guards (C ABI) reports any band a kernel has written into.
+// hipMalloc / hipFree, except under RB_GUARD=1 or 2 (test runs): every block is then surrounded by two 4 KiB guard bands filled
+// with a fixed byte, and rb_debug_check_guards (C ABI) reports any band a kernel has written into.  Under 1 the block itself is
+// zeroed; under 2 it is left at the fill byte as well (poison: a read of never-written memory then changes the result).
 hipError_t rb_dev_malloc(void** p, size_t bytes);
 void rb_dev_free(void* p);
 

@@ -425,7 +425,9 @@ def check_learn(lib, Mem, case, flagset="default", where="hip"):
     ads = [make_learner(lib, m, case + "-%d" % r, cfgd) for r in range(world)]
     try:
         stride = exchange_layout(lib, ads[0])[0]
-        local = [m.empty((stride,), np.float32) for _ in ads]
+        # include/rainbow_hip.h, rb_learner_set_exchange: "allocate the local block zero-filled" (the padding between the conv tensors
+        # is folded with the conv segment) — uploaded as zeros, so that a Mem whose empty() is not zero keeps the contract
+        local = [m.upload(np.zeros(stride, dtype=np.float32)) for _ in ads]
         gathered = [m.empty((world * stride,), np.float32) for _ in ads]
         for ad, lo, al in zip(ads, local, gathered):
             if flagset == "agent-flags":

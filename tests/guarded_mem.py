@@ -1,5 +1,10 @@
 """Caller-owned 'device' buffers with canaries: every allocation the test hands to the C ABI sits between two 4 KiB bands
-of a fixed byte; check() names any buffer whose bands a kernel wrote into.  Drop-in for cabi_adapter.NumpyMem / TorchMem."""
+of a fixed byte; check() names any buffer whose bands a kernel wrote into.  Drop-in for cabi_adapter.NumpyMem / TorchMem.
+
+Poisoned*Mem are the same with ONE difference: empty() leaves the user area at FILL instead of zeroing it, so a kernel that reads
+a caller-owned output buffer before writing it sees 0xC5 bytes (f32: a finite -6.3e3; an integer: nonsense), not the zeros every
+other Mem hands out.  upload() is unchanged.  A buffer whose contract in include/rainbow_hip.h says "zeroed by the caller" has to
+be uploaded as zeros by the adapter that owns it (tests/poison_run.py, tests/test_poison_*.py)."""
 import numpy as np
 
 from cabi_adapter import NumpyMem, TorchMem
@@ -9,6 +14,8 @@ FILL = 0xC5
 
 
 class GuardedNumpyMem(NumpyMem):
+    zero_fresh = True
+
     def __init__(self):
         self.blocks = []
 
@@ -16,7 +23,8 @@ class GuardedNumpyMem(NumpyMem):
         nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
         raw = np.full(nbytes + 2 * GUARD, FILL, dtype=np.uint8)
         user = raw[GUARD:GUARD + nbytes]
-        user[:] = 0
+        if self.zero_fresh:
+            user[:] = 0
         self.blocks.append((raw, nbytes, "%s%s" % (np.dtype(dtype).name, tuple(shape))))
         return user.view(dtype).reshape(shape)
 
@@ -32,6 +40,8 @@ class GuardedNumpyMem(NumpyMem):
 
 
 class GuardedTorchMem(TorchMem):
+    zero_fresh = True
+
     def __init__(self):
         super().__init__()
         self.blocks = []
@@ -42,7 +52,8 @@ class GuardedTorchMem(TorchMem):
         nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
         raw = t.full((nbytes + 2 * GUARD,), FILL, dtype=t.uint8, device=self.dev)
         user = raw[GUARD:GUARD + nbytes]
-        user.zero_()
+        if self.zero_fresh:
+            user.zero_()
         self.blocks.append((raw, nbytes, "%s%s" % (np.dtype(dtype).name, shape)))
         return user.view(getattr(t, self._map[np.dtype(dtype)])).reshape(shape)
 
@@ -59,3 +70,11 @@ class GuardedTorchMem(TorchMem):
             if not (bool((raw[:GUARD] == FILL).all()) and bool((raw[GUARD + n:] == FILL).all())):
                 bad.append(name)
         return len(self.blocks), bad
+
+
+class PoisonedNumpyMem(GuardedNumpyMem):
+    zero_fresh = False
+
+
+class PoisonedTorchMem(GuardedTorchMem):
+    zero_fresh = False
