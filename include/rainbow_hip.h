@@ -842,6 +842,75 @@ int rb_learner_target_ema(rb_learner_t* l, float tau, rb_stream_t stream);
 int rb_learner_shrink_perturb(rb_learner_t* l, float alpha_encoder, float alpha_head, float noisy_std, uint64_t seed, uint64_t draw,
                               int32_t with_target, float* exp_avg_dev, float* exp_avg_sq_dev, rb_stream_t stream);
 
+/* ---- device-side diagnostics (all off by default: with none of them used, every launch, grid and result is what it is
+ * without this section).
+ *
+ * Step records.  One 64-byte record per learn call, written by the device into a ring the caller owns and read whenever the
+ * caller likes: watching a loss curve no longer means reading a private buffer behind a synchronise after every step.   */
+typedef struct {
+  int64_t step;        /* the device step counter as this call's head kernel left it; -1 without one (rb_learner_set_step_counter) */
+  int32_t batch;       /* B */
+  int32_t status;      /* the call's batch status word (non-zero: the sampler gave up, the weights are zero); 0 without a sink */
+  float loss_mean, loss_max;      /* over loss_dev[b] (agent.py:94) */
+  float wloss_mean;               /* mean_b w_b * loss_b: the objective of agent.py:96 */
+  float weight_mean;              /* mean_b w_b */
+  float q_mean;                   /* mean_b sum_z support[z] * exp(log p(s_t, a_t)[b][z]): the online value of the taken action */
+  float q_target_mean;            /* mean_b sum_z support[z] * m[b][z]: the projected target's value */
+  float td_abs_mean;              /* mean_b |q_target_b - q_b| */
+  float entropy_mean;             /* mean_b -sum_z p log p of p(s_t, a_t) */
+  float return_mean;              /* mean_b returns[b] */
+  float terminal_frac;            /* share of rows with nonterminals[b] == 0 */
+  float grad_norm;                /* the gradient's global norm BEFORE the clip; NaN when the call left no partial list (below) */
+  float reserved;                 /* written as 0 */
+} rb_step_stats_t;                /* 64 bytes */
+
+/* ring_dev [capacity] records and count_dev (one device word, zeroed by the caller) are caller-owned; NULL / NULL (capacity is then
+ * ignored) switches the records off again.  With a ring set, every learn call — rb_learner_learn, rb_learner_learn_windows,
+ * rb_learner_train_step[_dist] — ends with ONE extra launch behind its last backward kernel, which writes the record at
+ * *count_dev % capacity and then increments *count_dev: both on the device, so a captured graph replays them correctly.  All 64
+ * bytes are written every time (the ring may be a never-zeroed allocation), nothing outside the ring and the word is.  The record
+ * is a fixed-order reduction (double accumulation, rows in index order): bit-identical from run to run.
+ *   grad_norm is summed from the partial sums of squares the backward kernels left, in the optimiser pass's own order, so it
+ *     equals bit for bit what that pass later stores to norm_dev; the list is read, not consumed.  It is NaN when the call left
+ *     none: the fallback kernels (RB_OPTS generic), and the replica exchange, where the gradient is complete only after
+ *     rb_learner_finish_grads.  It is always the norm of the gradient THIS call computed: a caller that changes grads_dev afterwards
+ *     and says so with rb_learner_grads_modified (an all-reduce over replicas) gets the norm of the changed gradient in norm_dev,
+ *     and the record keeps the local one: then neither NaN nor equal to norm_dev.
+ *   A failed draw gives a record with status != 0 and an unchanged step.
+ * The first call with a ring allocates a few KB of scratch in the handle, which synchronises the device once: make it before
+ * capturing a graph.  Reading: synchronise the stream the learn calls went to, copy *count_dev and the ring (rb_copy_to_host);
+ * record i of the run sits in slot i % capacity, and the records below *count_dev - capacity are overwritten.                  */
+int rb_learner_set_stats(rb_learner_t* l, rb_step_stats_t* ring_dev, int32_t capacity, int64_t* count_dev);
+
+/* Held-out loss: the learn step's three forwards and its head on a batch the caller supplies, and nothing else — no backward, no
+ * priority write-back, no noise draw, no optimiser pass.  Both networks run in eval mode (noise zero, model.py:46), so the result
+ * is deterministic; the targets use the handle's horizon (rb_learner_set_horizon) and unit importance weights.
+ *   loss_dev [B]: the per-sample cross-entropy.  stats_out_dev (may be NULL): ONE record of the batch, with step = -1, status = 0
+ *   and grad_norm = NaN; the ring of rb_learner_set_stats and its count are not touched.
+ * State rules of rb_learner_act_batch: a pending optimiser pass runs first.  It overwrites the activations of the last learn call,
+ * so it refuses (RB_ERR_STATE) while that call's gradients still wait for rb_learner_finish_grads or for the fused optimiser pass
+ * (RB_LEARNER_FUSE_FC_H_DW).  Parameters, target, moments, gradients and their norm partials, both noise buffers and the noise
+ * epoch, the step counter and the priority sink's tree are left unchanged, bit for bit.  The first call allocates scratch in the
+ * handle and synchronises once.                                                                                           */
+int rb_learner_eval_loss(rb_learner_t* l, const uint8_t* states_dev, const uint8_t* next_states_dev,
+                         const int64_t* actions_dev, const float* returns_dev, const float* nonterminals_dev,
+                         float* loss_dev, rb_step_stats_t* stats_out_dev, rb_stream_t stream);
+
+/* Priority statistics of a replay: one streamed pass over the `capacity` leaves of the sum tree (4 MB at 2^20 slots), in stream
+ * order.  A leaf that is NaN, infinite or negative counts as invalid and is excluded from everything else; zero leaves (empty
+ * slots, slots kept unsampleable) are counted nowhere.  Leaves are split over workgroups in fixed chunks, every workgroup leaves
+ * double partials, and the last one to arrive adds them in chunk order: the result is bit-identical when repeated.            */
+typedef struct {
+  int64_t nonzero, invalid;    /* leaves > 0 and finite; leaves that are NaN, inf or negative */
+  double sum, sumsq;           /* over the valid non-zero leaves (effective sample size = sum^2 / sumsq) */
+  float max, min_pos;          /* largest and smallest valid non-zero leaf; 0 and 0 for an empty tree */
+  int32_t hist[64];            /* bin k: valid non-zero leaves with floor(log2 p) == k - 40, clamped at both ends; the exponent is
+                                  read from the bit pattern, denormals go to bin 0 */
+} rb_priority_stats_t;
+/* out_dev is overwritten entirely.  Like every reader of the tree it waits for and discards an early draw in flight.  The partial
+ * scratch belongs to the handle: it is allocated by the first call, which synchronises the device once.                       */
+int rb_replay_priority_stats(rb_replay_t* r, rb_priority_stats_t* out_dev, rb_stream_t stream);
+
 /* White-box access for parity tests: copies an internal activation to out_dev.
  * what: 0 log_ps_a [B][atoms], 1 m (projected target) [B][atoms], 2 argmax a* i32[B],
  *       3 pns_a [B][atoms], 4 logits [3B][atoms*(actions+1)],

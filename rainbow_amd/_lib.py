@@ -48,6 +48,20 @@ class TrainStep(C.Structure):
                 ("step", c_int64), ("max_norm", c_float), ("reserved2", c_float)]
 
 
+class StepStats(C.Structure):
+    """rb_step_stats_t (include/rainbow_hip.h): one learn call, 64 bytes."""
+    _fields_ = [("step", c_int64), ("batch", c_int32), ("status", c_int32), ("loss_mean", c_float), ("loss_max", c_float),
+                ("wloss_mean", c_float), ("weight_mean", c_float), ("q_mean", c_float), ("q_target_mean", c_float),
+                ("td_abs_mean", c_float), ("entropy_mean", c_float), ("return_mean", c_float), ("terminal_frac", c_float),
+                ("grad_norm", c_float), ("reserved", c_float)]
+
+
+class PriorityStats(C.Structure):
+    """rb_priority_stats_t (include/rainbow_hip.h)."""
+    _fields_ = [("nonzero", c_int64), ("invalid", c_int64), ("sum", c_double), ("sumsq", c_double), ("max", c_float),
+                ("min_pos", c_float), ("hist", c_int32 * 64)]
+
+
 class TensorDesc(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("offset", c_int64), ("ndim", c_int32), ("shape", c_int32 * 4)]
 
@@ -190,6 +204,9 @@ SIGNATURES = {
     "rb_learner_get_rng": (c_int, [c_void_p, C.POINTER(c_uint64), C.POINTER(c_uint64), c_void_p]),
     "rb_learner_set_rng": (c_int, [c_void_p, c_uint64, c_uint64, c_void_p]),
     "rb_learner_debug_read": (c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
+    "rb_learner_set_stats": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "rb_learner_eval_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rb_replay_priority_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
 }
 
 
@@ -211,6 +228,7 @@ def declare(lib, strict=True):
 
 LEARNER_FUSE_FC_H_DW, LEARNER_WRITE_FUSED_GRADS, LEARNER_DEFER_UPDATE, LEARNER_IMPLICIT_SIGMA = 1, 2, 4, 8
 OBS_BLANK, OBS_FRAME_A, OBS_FRAME_B = 1, 2, 4          # RB_OBS_* (rb_obs_stack_step)
+PRIORITY_HIST_LO_EXP = -40                             # floor(log2 p) of rb_priority_stats_t.hist[0]
 
 
 class RainbowError(RuntimeError):

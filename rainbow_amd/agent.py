@@ -19,8 +19,8 @@ default, or one all-reduce of the flat buffer).  Enabled automatically when torc
 initialised.
 
 This module: construction, the mode flags, the parameter-space properties and operations, and the noise state.  The learn step
-is agent_learn.py, the act / evaluate paths agent_act.py, state_dict and checkpoints agent_state.py; the flat layout, its
-initial distributions and the optimiser are params.py.
+is agent_learn.py, the act / evaluate paths agent_act.py, state_dict and checkpoints agent_state.py, the step records and the
+held-out loss agent_stats.py; the flat layout, its initial distributions and the optimiser are params.py.
 """
 import ctypes as C
 import os
@@ -34,10 +34,11 @@ from ._util import current_stream_handle, u64_pair
 from .agent_act import AgentAct
 from .agent_learn import AgentLearn
 from .agent_state import AgentState
+from .agent_stats import AgentStats
 from .params import _FlatAdam, _query_layout, init_parameters_flat
 
 
-class Agent(AgentLearn, AgentAct, AgentState):
+class Agent(AgentLearn, AgentAct, AgentState, AgentStats):
     _h = None                  # (so that __del__ is safe on an object whose construction failed early)
 
     def __init__(self, args, env):
@@ -181,6 +182,10 @@ class Agent(AgentLearn, AgentAct, AgentState):
         self._reset_shrink = (0.5 if enc is None else float(enc), 0.0 if head is None else float(head))
         self._reset_seed = int(getattr(args, "seed", 0) or 0)
         self.resets = 0
+        # args.step_stats = capacity: one rb_step_stats_t per learn() in a device ring, read with read_stats() (agent_stats.py).
+        # Absent or 0 (the default): no ring, no extra launch.
+        if int(getattr(args, "step_stats", 0) or 0) > 0:
+            self.track_stats(int(args.step_stats))
 
     # The flat tensors the library borrows.  With a deferred optimiser pass pending they are one update behind: reading them
     # through these names runs the pass first.

@@ -17,7 +17,7 @@
 // This file keeps the handle's lifecycle and the step itself (learn_impl, train_step_impl and their entry points).  Its sections:
 //   learner_internal.h  layout, RB_OPTS, the handle          learner_plan.h     which kernel a shape reaches (pure functions)
 //   head.h / grad_finish.h / adam_kernels.h / noise_kernel.h  kernels           conv_dispatch.h / fc_dispatch.h   the launches
-//   noisy_rows.h  the per-row-noise act layers (kernels)
+//   noisy_rows.h  the per-row-noise act layers (kernels)         learn_stats.h  the step records and the held-out loss
 //   optimizer_host.h / act_host.h / exchange_host.h / layout_api.h / launch_plan_debug.h   the other entry points, by concern
 // Each is included HERE and nowhere else (they define non-template kernels and static functions).
 #include "learner_internal.h"
@@ -32,6 +32,7 @@
 #include "fc_dispatch.h"
 #include "optimizer_host.h"
 #include "param_reset.h"
+#include "learn_stats.h"
 #include "act_host.h"
 #include "exchange_host.h"
 #include "layout_api.h"
@@ -84,6 +85,9 @@ int rb_learner_destroy(rb_learner_t* l) {
   if (l->status_copy) rb_dev_free(l->status_copy);
   if (l->adam_args_dev) rb_dev_free(l->adam_args_dev);
   if (l->go_flag) rb_dev_free(l->go_flag);
+  if (l->stats_rows) rb_dev_free(l->stats_rows);
+  if (l->stats_ticket) rb_dev_free(l->stats_ticket);
+  if (l->ones) rb_dev_free(l->ones);
   delete l;
   return RB_OK;
 }
@@ -348,7 +352,8 @@ static int learn_impl(rb_learner_t* l, const ImgSrc& src, const uint8_t* states_
     RB_LAUNCH(k_reduce_conv_dw_all, dim3(plan_conv_reduce_blocks(L, ra.snap_n > 0)), dim3(64), stream, ra);
     RB_LAUNCH_CHECK();
   }
-  return RB_OK;
+  // with a record ring set (rb_learner_set_stats): this call's rb_step_stats_t, one launch (learn_stats.h); otherwise nothing
+  return learn_step_stats(l, loss_dev, weights_dev, returns_dev, nonterminals_dev, stream);
 }
 
 int rb_learner_learn(rb_learner_t* l, const uint8_t* states_dev, const uint8_t* next_states_dev,

@@ -269,6 +269,14 @@ struct rb_learner {
   int32_t n_eff;        // the effective horizon (rb_learner_set_horizon; cfg.multi_step until then): the next-state slot of the window
   double discount;      // table (SrcDesc n_step) and the exponent of gamma_n — host state, read when a step is launched
   float delta_z;        // float32((Vmax - Vmin)/(Z-1))   agent.py:19,82
+  // device-side read-outs (learn_stats.h): the caller's record ring (rb_learner_set_stats; NULL = off, no launch) and the scratch
+  // k_step_stats and rb_learner_eval_loss need, allocated by the first of them that is used
+  rb_step_stats_t* stats_ring;
+  long long* stats_count;
+  int stats_cap;
+  double* stats_rows;       // [3][B] per-row q, q_target, entropy
+  unsigned* stats_ticket;   // arrival counter of k_step_stats (self-resetting)
+  float* ones;              // [B] unit importance weights of rb_learner_eval_loss
 };
 
 // ---- host functions called across the learner's files

@@ -22,6 +22,7 @@
 #include "replay_sample.h"
 #include "replay_shift.h"
 #include "replay_view.h"
+#include "replay_stats.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -72,6 +73,7 @@ struct rb_replay {
                                   // the public sample entry points always redraw into table 0 = rb_replay_buffers_t.window_dev)
   int spec_disabled;              // an expired cross-stream wait was seen (fail_host[2]): no early draw on this handle until
                                   // rb_replay_reset_failed_samples
+  PriorityScratch* pstats;        // per-workgroup partials of rb_replay_priority_stats (replay_stats.h), allocated by its first call
 };
 static int32_t* win_of(const rb_replay* r, int set) { return set ? r->win2 : r->win; }
 // every entry point that reads or writes the replay outside a draw: wait for an early draw in flight and discard it (its
@@ -290,6 +292,7 @@ int rb_replay_destroy(rb_replay_t* r) {
   if (r->spec_stream) (void)hipStreamDestroy(r->spec_stream);
 #endif
   live_del(r);
+  if (r->pstats) rb_dev_free(r->pstats);
   if (r->win2) rb_dev_free(r->win2);
   if (r->spec_res) rb_dev_free(r->spec_res);
   if (r->tree) rb_dev_free(r->tree);
@@ -688,6 +691,25 @@ int rb_replay_states_at(rb_replay_t* r, const int64_t* data_index_dev, int32_t n
 }
 
 // ---------------------------------------------------------------------- counters --
+// The shape of the priority distribution (include/rainbow_hip.h; replay_stats.h k_priority_stats): a read of the leaves, in stream order.
+int rb_replay_priority_stats(rb_replay_t* r, rb_priority_stats_t* out_dev, rb_stream_t stream) {
+  RB_REQUIRE(r != nullptr, "rb_replay_priority_stats: NULL handle (r)");
+  RB_REQUIRE(out_dev != nullptr, "rb_replay_priority_stats: NULL out_dev");
+  RB_SPEC_JOIN(r);
+  if (!r->pstats) {
+    RB_HIP_TRY(rb_dev_malloc((void**)&r->pstats, sizeof(PriorityScratch)));
+    RB_HIP_TRY(hipMemset(r->pstats, 0, sizeof(PriorityScratch)));      // the counters start at zero and put themselves back
+  }
+  PriorityStatsArgs a;
+  a.leaves = r->tree + r->tree_start; a.capacity = r->capacity;
+  a.chunk = rb_div_up(rb_div_up(r->capacity, RB_PSTATS_MAX_WG), RB_PSTATS_THREADS) * RB_PSTATS_THREADS;
+  if (a.chunk < RB_PSTATS_MIN_CHUNK) a.chunk = RB_PSTATS_MIN_CHUNK;
+  a.scratch = r->pstats; a.out = out_dev;
+  RB_LAUNCH(k_priority_stats, dim3((unsigned)rb_div_up(r->capacity, a.chunk)), dim3(RB_PSTATS_THREADS), stream, a);
+  RB_LAUNCH_CHECK();
+  return RB_OK;
+}
+
 int rb_replay_streams(rb_replay_t* r, int32_t* streams) {
   RB_REQUIRE(r && streams, "rb_replay_streams: NULL argument");
   *streams = r->streams;

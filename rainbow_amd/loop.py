@@ -35,20 +35,24 @@ def horizon_at(t, n0, n1, g0, g1, T):
     return n, 1 - (1 - g0) * ((1 - g1) / (1 - g0)) ** f
 
 
-def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states, round_fn):
+def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states, round_fn, on_log=None):
     """The cadence of main.py:146-184 at S environment steps per round, shared by train_device and train_host_vec:
     round_fn(states) acts, steps the environment and appends the round to `mem`, and returns the next states.
     args.multi_step_final (absent: no schedule, set_horizon is never called) anneals the horizon from args.multi_step and, with
     args.discount_final, the discount from args.discount (horizon_at) over args.horizon_anneal_steps (10 000) gradient steps counted
     from the start or the last reset: agent and memory are set before the first learn step, before every learn step whose count t is
     a multiple of args.horizon_update_interval (100) up to the end of the anneal, at t = horizon_anneal_steps, and right after each
-    agent.reset_parameters(), which restarts t at 0."""
+    agent.reset_parameters(), which restarts t at 0.
+    on_log (None: nothing is read, nothing changes): called as on_log(T, agent.read_stats()) right after every learn step whose
+    count is a multiple of args.log_interval (in learn steps; absent or 0: never) — the records of the steps since the last call
+    (Agent.track_stats / args.step_stats; None when the agent keeps none).  read_stats synchronises; the steps in between do not."""
     seed = int(getattr(args, "seed", 0))
     increase = (1 - args.priority_weight) / (T_max - args.learn_start)           # main.py:123
     eval_every = int(getattr(args, "evaluation_interval", 0) or 0)
     replay_ratio = float(getattr(args, "replay_ratio", 0) or 0)                   # learn steps per environment step; may exceed 1
     reset_interval = int(getattr(args, "reset_interval", 0) or 0)                 # in GRADIENT steps; 0 = never
     learn_owed, learns = 0.0, 0
+    log_interval = int(getattr(args, "log_interval", 0) or 0) if on_log is not None else 0
     n1 = getattr(args, "multi_step_final", None)
     set_horizon = None
     if n1 is not None:
@@ -85,6 +89,8 @@ def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states,
                 learn_owed -= 1
                 learns += 1
                 since_reset += 1
+                if log_interval and learns % log_interval == 0:
+                    on_log(T, agent.read_stats())
                 if reset_interval and learns % reset_interval == 0:
                     agent.reset_parameters()                                      # shrink-and-perturb (Agent.reset_parameters)
                     since_reset = 0
@@ -99,7 +105,7 @@ def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states,
     return learns
 
 
-def train_device(agent, mem, env, args, T_max, on_eval=None, per_stream_noise=False):
+def train_device(agent, mem, env, args, T_max, on_eval=None, per_stream_noise=False, on_log=None):
     """main.py:146-184 for S = env.streams device streams (INTEGRATION.md §2): T counts environment steps, S per round;
     reset_noise once per replay_frequency env steps; from learn_start on, beta is annealed by priority_weight_increase * S per
     round, one learn() per replay_frequency env steps (learn_owed), target update and evaluation at `T % k < S`.
@@ -116,6 +122,8 @@ def train_device(agent, mem, env, args, T_max, on_eval=None, per_stream_noise=Fa
     per_stream_noise=True: every stream acts under its OWN noisy-net sample — agent.reset_noise_rows(S, rng=(args.seed, T)) at
     the cadence of reset_noise() (which stays: learn() needs the learner's own sample) and act_batch(per_row_noise=True);
     the default leaves today's launches exactly as they are (all S streams share the one online sample).
+    on_log(T, records), if given, is called every args.log_interval LEARN steps with agent.read_stats(): the per-step records the
+    device has written since the last call (args.step_stats / Agent.track_stats); it synchronises, nothing else in the loop does.
     Returns the number of learn() calls made."""
     S = env.streams
     if S != mem.streams:
@@ -137,10 +145,10 @@ def train_device(agent, mem, env, args, T_max, on_eval=None, per_stream_noise=Fa
     states = env.reset()
     if S == 1:
         states = states.unsqueeze(0)
-    return _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states, round_fn)
+    return _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states, round_fn, on_log)
 
 
-def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None, per_stream_noise=False):
+def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None, per_stream_noise=False, on_log=None):
     """main.py:146-184 for S = len(emus) raw host emulators behind `front`, a rainbow_amd.frames.FrameStackVec (INTEGRATION.md
     §2).  emus[s] is duck-typed:
         reset(out_a)                 starts the next game — or, after a step that reported life_lost, does env.py:36-38's
@@ -158,7 +166,8 @@ def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None, per_strea
     Cadences are train_device's: reset_noise once per replay_frequency env steps; from learn_start on, beta annealed by
     priority_weight_increase * S per round, one learn() per replay_frequency env steps (learn_owed) — or S * args.replay_ratio
     per round, with agent.reset_parameters() every args.reset_interval gradient steps, as in train_device — target update and
-    on_eval at `T % k < S`; args.multi_step_final and its companions anneal the horizon as in train_device.  per_stream_noise: as in train_device (one noise sample per emulator).  Returns the number of learn() calls made."""
+    on_eval at `T % k < S`; args.multi_step_final and its companions anneal the horizon as in train_device.  per_stream_noise: as in train_device (one noise sample per emulator); on_log and args.log_interval: as in train_device.
+    Returns the number of learn() calls made."""
     S = len(emus)
     if S != mem.streams or S != front.streams:
         raise ValueError("train_host_vec: %d emulators, a front end of %d streams, a memory of %d" % (S, front.streams, mem.streams))
@@ -184,7 +193,7 @@ def train_host_vec(agent, mem, emus, front, args, T_max, on_eval=None, per_strea
     scr = front.screens
     for s in range(S):
         emus[s].reset(scr[s, 0])
-    return _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, front.reset_all(), round_fn)
+    return _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, front.reset_all(), round_fn, on_log)
 
 
 def evaluate_device(agent, env, episodes):
@@ -211,11 +220,15 @@ def evaluate_device(agent, env, episodes):
     return st["mean_return"]
 
 
-def _evaluation_result(agent, returns, lengths, val_mem):
+def _evaluation_result(agent, returns, lengths, val_mem, with_loss=False):
     rewards = [float(x) for x in returns]                                         # test.py:33 T_rewards
     Qs = agent.evaluate_q_memory(val_mem) if val_mem is not None else None        # test.py:38-39
-    return dict(avg_reward=sum(rewards) / len(rewards), rewards=rewards, lengths=[int(x) for x in lengths],      # test.py:41
-                avg_Q=float(sum(float(q) for q in Qs) / len(Qs)) if Qs is not None else None, Qs=Qs)
+    out = dict(avg_reward=sum(rewards) / len(rewards), rewards=rewards, lengths=[int(x) for x in lengths],      # test.py:41
+               avg_Q=float(sum(float(q) for q in Qs) / len(Qs)) if Qs is not None else None, Qs=Qs)
+    if with_loss and val_mem is not None:         # the held-out loss and TD error (Agent.evaluate_loss): the overfitting signal
+        ev = agent.evaluate_loss(val_mem)
+        out["val_loss"], out["val_td_abs"] = ev["loss_mean"], ev["td_abs_mean"]
+    return out
 
 
 @contextmanager
@@ -234,7 +247,7 @@ def _unfinished(who, missing, episodes, max_rounds):
     return RuntimeError("%s: %d of %d episodes still unfinished after max_rounds = %d rounds" % (who, missing, episodes, max_rounds))
 
 
-def evaluate_vec(agent, env, episodes, epsilon=0.001, seed=0, val_mem=None, poll_every=8, max_rounds=None):
+def evaluate_vec(agent, env, episodes, epsilon=0.001, seed=0, val_mem=None, poll_every=8, max_rounds=None, with_loss=False):
     """test.py:13-41 on `env`, a rainbow_amd.envs environment of S streams with a seed of its own: the agent in eval() mode,
     act_e_greedy with `epsilon` for every stream (Agent.act_batch(epsilon=..., rng=(seed, round)): the draw happens in the head
     kernel), raw rewards, and the list of episode returns the reference calls T_rewards.  A round is act -> env.step_device ->
@@ -246,6 +259,8 @@ def evaluate_vec(agent, env, episodes, epsilon=0.001, seed=0, val_mem=None, poll
     env.eval() before the call; a training-mode environment would have every life recorded as an episode.
     Returns dict(avg_reward, rewards, lengths, avg_Q, Qs): `rewards` has exactly `episodes` entries; Qs is
     agent.evaluate_q_memory(val_mem) (test.py:38-39) and avg_Q its mean when a validation memory is given, else None.
+    with_loss=True (and a validation memory that is a rainbow_amd ReplayMemory): also val_loss / val_td_abs, the loss and the mean
+    |target value - online value| of one batch drawn from it (Agent.evaluate_loss; it advances val_mem's draw state).
     The agent is left in the mode it came in."""
     S = env.streams
     poll_every = max(1, int(poll_every))
@@ -269,16 +284,16 @@ def evaluate_vec(agent, env, episodes, epsilon=0.001, seed=0, val_mem=None, poll
                     raise _unfinished("evaluate_vec", missing, episodes, max_rounds)
         returns, lengths, _ = tally.result()
         tally.close()
-        return _evaluation_result(agent, returns, lengths, val_mem)
+        return _evaluation_result(agent, returns, lengths, val_mem, with_loss)
 
 
-def evaluate_host_vec(agent, emus, front, episodes, epsilon=0.001, seed=0, val_mem=None, max_rounds=None):
+def evaluate_host_vec(agent, emus, front, episodes, epsilon=0.001, seed=0, val_mem=None, max_rounds=None, with_loss=False):
     """The same protocol for S = len(emus) raw host emulators behind `front`, a rainbow_amd.frames.FrameStackVec, duck-typed as
     in train_host_vec.  The emulators are the caller's EVALUATION ones: env.py's eval mode reports no life-loss terminals
     (env.py:70-75 is training only), so a step that reports life_lost raises ValueError.  A stream whose step ended its game
     is reset in the same round with front.RESET.  Rewards are host values here, so the tally rule of rb_tally_* (even quotas,
     f32 running return, the ending step's reward belongs to the ending episode, stream-major list) is kept in numpy.
-    Returns what evaluate_vec returns; more than `max_rounds` rounds raise RuntimeError."""
+    Returns what evaluate_vec returns (with_loss as there); more than `max_rounds` rounds raise RuntimeError."""
     S = len(emus)
     if S != front.streams:
         raise ValueError("evaluate_host_vec: %d emulators, a front end of %d streams" % (S, front.streams))
@@ -317,4 +332,4 @@ def evaluate_host_vec(agent, emus, front, episodes, epsilon=0.001, seed=0, val_m
             states = front.step(flags)
             rounds += 1
         flat = [x for per_stream in recorded for x in per_stream]
-        return _evaluation_result(agent, [x[0] for x in flat], [x[1] for x in flat], val_mem)
+        return _evaluation_result(agent, [x[0] for x in flat], [x[1] for x in flat], val_mem, with_loss)

@@ -441,3 +441,20 @@ class ReplayMemory(ReplayAppend, ReplayState):
         self._keep["idx"] = idx
         L.check(self._lib, self._lib.rb_replay_states_at(self._handle, idx.data_ptr(), n, out.data_ptr(), self._stream()))
         return out
+
+    def priority_stats(self):
+        """The shape of the priority distribution (rb_replay_priority_stats: one streamed pass over the leaves, on the device).
+        A pending lazy update_priorities() is applied first, as a draw does; then the stream is synchronised.  Returns a dict:
+        nonzero / invalid (leaf counts; invalid = NaN, inf or negative, excluded from the rest), sum, sumsq, max, min_pos (0 for
+        an empty memory), ess = sum^2 / sumsq (the effective sample size; 0.0 when empty), hist (int32 [64]: bin k counts the
+        leaves with floor(log2 p) == hist_lo_exp + k, clamped at both ends) and hist_lo_exp = -40."""
+        if self._pending is not None:
+            self.flush()
+        out = self._keep.get("pstats")
+        if out is None:
+            out = self._keep["pstats"] = torch.empty(C.sizeof(L.PriorityStats), dtype=torch.uint8, device=self.device)
+        L.check(self._lib, self._lib.rb_replay_priority_stats(self._h, out.data_ptr(), self._stream()))
+        s = L.PriorityStats.from_buffer_copy(out.cpu().numpy().tobytes())      # (the copy synchronises)
+        return dict(nonzero=int(s.nonzero), invalid=int(s.invalid), sum=float(s.sum), sumsq=float(s.sumsq), max=float(s.max),
+                    min_pos=float(s.min_pos), ess=(s.sum * s.sum / s.sumsq) if s.sumsq > 0 else 0.0,
+                    hist=np.array(s.hist, dtype=np.int32), hist_lo_exp=L.PRIORITY_HIST_LO_EXP)

@@ -14,7 +14,10 @@ pixels, the learn step on the gathered path).  `--target-tau TAU` gives the agen
 every optimiser step inside the clip + Adam pass, and the loop makes no hard target syncs).  `--replay-ratio R` makes R learn steps
 per environment step (args.replay_ratio; the recipe's replay_frequency = 1 is ratio 1) and `--reset-interval N` shrinks and perturbs
 the networks every N GRADIENT steps (args.reset_interval: Agent.reset_parameters with its defaults, encoder 0.5 / head 0); the line
-then carries both and the number of resets done."""
+then carries both and the number of resets done.
+`--stats` keeps the device's per-step records (args.step_stats, rainbow_amd/agent_stats.py) and reads them every --log-interval learn
+steps (train_device's on_log): each checkpoint then also shows the means since the checkpoint before it of the loss, the online value
+q, the |target - online| value gap td and the gradient norm g — why a curve moves or does not, not only whether it does."""
 import argparse
 import os
 import sys
@@ -40,7 +43,7 @@ def options(t_max, dev, multi_step=20, learn_start=1600, augment_pad=0, target_t
 
 
 def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", multi_step=20, learn_start=1600, augment_pad=0,
-        target_tau=0.0, replay_ratio=0.0, reset_interval=0):
+        target_tau=0.0, replay_ratio=0.0, reset_interval=0, stats=False, log_interval=200):
     from rainbow_amd.agent import Agent
     from rainbow_amd.envs import BreakoutVec, CatchVec
     from rainbow_amd.loop import evaluate_device, evaluate_vec, train_device
@@ -49,6 +52,8 @@ def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", mul
     args = options(t_max, dev, multi_step, learn_start, augment_pad, target_tau, replay_ratio, reset_interval)
     args.evaluation_interval = t_eval
     args.seed = seed
+    if stats and learn:
+        args.step_stats, args.log_interval = 4 * log_interval, log_interval
     np.random.seed(seed)
     torch.manual_seed(np.random.randint(1, 10000))
     env = make(S, dev, seed=seed)
@@ -58,19 +63,34 @@ def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", mul
     if not learn:
         agent.learn = lambda mem: None
     curve = []
+    seen = {k: [] for k in ("loss_mean", "q_mean", "td_abs_mean", "grad_norm")}      # the records since the last checkpoint
+    dropped = [0]
+
+    def on_log(T, records):
+        for k in seen:
+            seen[k].append(records[k])
+        dropped[0] += records["dropped"]
+
+    def stats_columns():
+        if not (stats and learn) or not seen["loss_mean"]:
+            return ""
+        m = {k: float(np.nanmean(np.concatenate(v))) for k, v in seen.items()}
+        for v in seen.values():
+            del v[:]
+        return "[loss %.3f q %+.3f td %.3f g %.2f]" % (m["loss_mean"], m["q_mean"], m["td_abs_mean"], m["grad_norm"])
 
     def on_eval(T):
         ev = make(16, dev, seed=EVAL_SEED)
         ev.eval()
         if protocol == "vec":
-            curve.append((T, evaluate_vec(agent, ev, 256, seed=T)["avg_reward"]))
+            curve.append((T, evaluate_vec(agent, ev, 256, seed=T)["avg_reward"], stats_columns()))
         else:
-            curve.append((T, evaluate_device(agent, ev, 256)))
+            curve.append((T, evaluate_device(agent, ev, 256), stats_columns()))
         ev.close()
 
     t0 = time.perf_counter()
     try:
-        train_device(agent, mem, env, args, t_max, on_eval=on_eval)
+        train_device(agent, mem, env, args, t_max, on_eval=on_eval, on_log=on_log if stats and learn else None)
         note = ""
     except RuntimeError as e:
         note = "  STOPPED: " + str(e)[:150]
@@ -79,7 +99,7 @@ def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", mul
     if replay_ratio or reset_interval:
         tag += " replay-ratio %g reset-interval %d (%d resets)" % (replay_ratio or 1.0, reset_interval, agent.resets)
     print("S %2d seed %3d %s (%.1f s): " % (S, seed, tag, time.perf_counter() - t0)
-          + " ".join("%d:%+.3f" % c for c in curve) + "  training-episode mean %+.3f" % env.stats()["mean_return"] + note,
+          + " ".join("%d:%+.3f%s" % c for c in curve) + ("  (%d records dropped)" % dropped[0] if dropped[0] else "") + "  training-episode mean %+.3f" % env.stats()["mean_return"] + note,
           flush=True)
     env.close()
 
@@ -99,6 +119,8 @@ def main():
     ap.add_argument("--target-tau", type=float, default=0.0)
     ap.add_argument("--replay-ratio", type=float, default=0.0)
     ap.add_argument("--reset-interval", type=int, default=0)
+    ap.add_argument("--stats", action="store_true")
+    ap.add_argument("--log-interval", type=int, default=200)
     a = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
@@ -106,7 +128,7 @@ def main():
     for S in a.streams:
         for k in range(a.seeds if S == 1 else min(3, a.seeds)):
             run(S, 101 + 7 * k, a.t_max, a.t_eval, not a.no_learn, dev, a.protocol, a.env, a.multi_step, a.learn_start, a.augment_pad,
-                a.target_tau, a.replay_ratio, a.reset_interval)
+                a.target_tau, a.replay_ratio, a.reset_interval, a.stats, a.log_interval)
 
 
 if __name__ == "__main__":
