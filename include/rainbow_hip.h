@@ -911,6 +911,53 @@ typedef struct {
  * scratch belongs to the handle: it is allocated by the first call, which synchronises the device once.                       */
 int rb_replay_priority_stats(rb_replay_t* r, rb_priority_stats_t* out_dev, rb_stream_t stream);
 
+/* ---- dormant units (ReDo: Sokar, Agarwal, Castro, Evci, "The Dormant Neuron Phenomenon in Deep RL", ICML 2023): a targeted reset
+ * and the diagnostic that goes with it.  Never on the per-step path: a run that does not call these launches what it launched before.
+ *
+ * A UNIT is an output channel of a conv layer or a hidden unit of fc_h_v / fc_h_a.  The layers, in this order: conv 0 .. nconv - 1
+ * (cout units each), fc_h_v (hidden units), fc_h_a (hidden units); U = the sum, the units numbered in that order.
+ * rb_learner_unit_layout: *n_layers = nconv + 2 and units_per_layer[5] (may be NULL; entries beyond n_layers are 0).
+ *   Incoming parameters of unit i: conv layer l: row i of convs.l.weight and convs.l.bias[i]; hidden unit j of stream s: row
+ *   s * hidden + j of fc_h weight_mu and weight_sigma, and its bias_mu and bias_sigma.
+ *   Outgoing parameters: conv l < nconv - 1: the ks^2 floats at o * K' + i * ks^2 of every row o of the next conv weight; the last
+ *   conv layer: columns [i P, (i + 1) P) of all 2 * hidden rows of fc_h weight_mu and weight_sigma; hidden unit j of stream v / a:
+ *   column j of fc_z_v's / fc_z_a's weight_mu and weight_sigma.                                                                */
+int rb_learner_unit_layout(const rb_learner_config_t* cfg, int32_t* n_layers, int32_t* units_per_layer);
+
+/* The ONLINE network's forward in eval mode (noise zero, as rb_learner_eval_loss) on B = cfg.batch states u8 [B][history][84][84] —
+ * no target rows, no head — then ONE launch that writes (accumulate == 0) or adds to (!= 0)
+ *   activity_dev[i] = sum over the B rows and the unit's positions of its post-ReLU activation          double [U]
+ * accumulated in double in a fixed order: a repeated call is bit-identical.  State rules of rb_learner_eval_loss: a pending
+ * optimiser pass runs first; RB_ERR_STATE while the last learn call's gradients wait for rb_learner_finish_grads or for the fused
+ * optimiser pass (the call overwrites that call's activations); parameters, target, moments, gradients and their norm partials,
+ * both noise buffers and the noise epoch, the step counter and the priority sink's tree are unchanged, bit for bit.             */
+int rb_learner_unit_activity(rb_learner_t* l, const uint8_t* states_dev, int32_t accumulate, double* activity_dev, rb_stream_t stream);
+
+/* ONE launch.  S_l = the fixed-order double sum of layer l's N_l activities; unit i is dormant iff activity[i] * N_l <= tau * S_l in
+ * double — the paper's s_i = E|h_i| / mean_k E|h_k| <= tau without the division (the sample count cancels inside a layer).  An
+ * all-zero layer is dormant as a whole.  A NaN makes the comparison false: a unit whose activity is NaN is never recycled, and a NaN
+ * in a layer (S_l is then NaN) recycles nothing in that layer.
+ *   mask_dev u8 [U]: 1 = dormant.  counts_dev i32 [n_layers]: dormant units per layer.  scores_dev float [U] (may be NULL):
+ *   (float)(activity[i] * N_l / S_l), 0 where S_l == 0.  tau must be finite and >= 0 (NaN too is RB_ERR_INVALID).                */
+int rb_learner_dormant_mask(rb_learner_t* l, const double* activity_dev, double tau, uint8_t* mask_dev, int32_t* counts_dev,
+                            float* scores_dev, rb_stream_t stream);
+
+/* The targeted reset.  A pending optimiser pass runs FIRST; then ONE launch in stream order: the mask is never read by the host and
+ * nothing synchronises.  For every unit with mask_dev[i] != 0:
+ *   incoming parameters <- phi, a fresh draw from the tensor's initial distribution (the bounds and constants of
+ *     rb_learner_shrink_perturb).  phi of flat element e is word e & 3 of Philox4x32-10(key = seed ^ 0x5245444F, counter hi = draw,
+ *     lo = e >> 2): u = (float)(x >> 8) * 2^-24, phi = bound * (2u - 1); the sigma tensors take their constant.  phi is written
+ *     without reading theta (a NaN does not survive) and depends on (seed, draw, e) alone: not on which other units are dormant.
+ *   outgoing parameters: weight_mu and conv weights <- 0, weight_sigma <- its initial constant, so that the eval-mode function of
+ *     the network is unchanged and the unit starts like a fresh noisy connection.  An element that is incoming to one dormant unit
+ *     and outgoing from another gets the outgoing rule (zero wins).
+ *   exp_avg_dev / exp_avg_sq_dev [n_params] (both or neither; NULL = none): zeroed at every written element.
+ *   with_target != 0: the target parameters get the same values, the same phi.
+ * Everything else is neither read nor written: the elements of units that are not dormant, the alignment padding, the output layer's
+ * biases, gradients, noise, the step counter.  With no dormant unit no byte changes.                                            */
+int rb_learner_recycle_units(rb_learner_t* l, const uint8_t* mask_dev, float noisy_std, uint64_t seed, uint64_t draw,
+                             int32_t with_target, float* exp_avg_dev, float* exp_avg_sq_dev, rb_stream_t stream);
+
 /* White-box access for parity tests: copies an internal activation to out_dev.
  * what: 0 log_ps_a [B][atoms], 1 m (projected target) [B][atoms], 2 argmax a* i32[B],
  *       3 pns_a [B][atoms], 4 logits [3B][atoms*(actions+1)],

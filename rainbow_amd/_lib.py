@@ -207,6 +207,10 @@ SIGNATURES = {
     "rb_learner_set_stats": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "rb_learner_eval_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rb_replay_priority_stats": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "rb_learner_unit_layout": (c_int, [C.POINTER(LearnerConfig), C.POINTER(c_int32), C.POINTER(c_int32)]),
+    "rb_learner_unit_activity": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "rb_learner_dormant_mask": (c_int, [c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rb_learner_recycle_units": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_int32, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -20,7 +20,7 @@ initialised.
 
 This module: construction, the mode flags, the parameter-space properties and operations, and the noise state.  The learn step
 is agent_learn.py, the act / evaluate paths agent_act.py, state_dict and checkpoints agent_state.py, the step records and the
-held-out loss agent_stats.py; the flat layout, its initial distributions and the optimiser are params.py.
+held-out loss agent_stats.py, the dormant-unit diagnostic and recycling agent_redo.py; the flat layout, its initial distributions and the optimiser are params.py.
 """
 import ctypes as C
 import os
@@ -34,11 +34,12 @@ from ._util import current_stream_handle, u64_pair
 from .agent_act import AgentAct
 from .agent_learn import AgentLearn
 from .agent_state import AgentState
+from .agent_redo import AgentRedo
 from .agent_stats import AgentStats
 from .params import _FlatAdam, _query_layout, init_parameters_flat
 
 
-class Agent(AgentLearn, AgentAct, AgentState, AgentStats):
+class Agent(AgentLearn, AgentAct, AgentState, AgentStats, AgentRedo):
     _h = None                  # (so that __del__ is safe on an object whose construction failed early)
 
     def __init__(self, args, env):
@@ -182,6 +183,11 @@ class Agent(AgentLearn, AgentAct, AgentState, AgentStats):
         self._reset_shrink = (0.5 if enc is None else float(enc), 0.0 if head is None else float(head))
         self._reset_seed = int(getattr(args, "seed", 0) or 0)
         self.resets = 0
+        # recycling dormant units (agent_redo.py: dormant_stats / recycle_dormant): the threshold's default and the number of
+        # recycles done so far, the `draw` word of the next one (checkpoint() / restore() carry it)
+        self._redo_tau = getattr(args, "redo_tau", None)
+        self.recycles = 0
+        self.last_recycle_counts = None
         # args.step_stats = capacity: one rb_step_stats_t per learn() in a device ring, read with read_stats() (agent_stats.py).
         # Absent or 0 (the default): no ring, no extra launch.
         if int(getattr(args, "step_stats", 0) or 0) > 0:

@@ -89,8 +89,8 @@ class AgentState:
     def checkpoint(self, path=None):
         """Everything the learner needs to continue bit-for-bit: online / target parameters (a pending optimiser pass, which
         with target_tau > 0 moves the target too, has run before they are copied), target_tau, both noise buffers, Adam
-        moments + step, the Philox (seed, epoch) of the noise generator, the pending-resample flag, the number of resets done
-        (reset_parameters: the next reset's draw) and the effective (horizon, discount) of set_horizon.  The reference's
+        moments + step, the Philox (seed, epoch) of the noise generator, the pending-resample flag, the numbers of resets and recycles done
+        (reset_parameters / recycle_dormant: the next one's draw) and the effective (horizon, discount) of set_horizon.  The reference's
         save() (weights only, agent.py:106-107) stays what main.py:182 calls; this is the superset a resumable run needs
         (main.py has no such thing: it restarts the optimiser).  Returns the dict; writes it with torch.save if `path`."""
         if not isinstance(self.optimiser, _FlatAdam):
@@ -104,7 +104,7 @@ class AgentState:
                   noise=self.noise.cpu(), target_noise=self.target_noise.cpu(), exp_avg=st["exp_avg"].cpu(),
                   exp_avg_sq=st["exp_avg_sq"].cpu(), adam_step=float(st["step"]), rng_seed=int(seed.value),
                   rng_epoch=int(epoch.value), noise_pending=bool(self._noise_pending), training=bool(self.training),
-                  target_tau=float(self._target_tau), resets=int(self.resets),
+                  target_tau=float(self._target_tau), resets=int(self.resets), recycles=int(self.recycles),
                   horizon=int(self.horizon), discount=float(self.discount))
         if path is not None:
             torch.save(ck, path)
@@ -137,6 +137,7 @@ class AgentState:
         if "target_tau" in ck:                      # (checkpoints from before the EMA target carry none: the agent keeps its own)
             self.target_tau = ck["target_tau"]
         self.resets = int(ck.get("resets", 0))      # (none before reset_parameters existed: no reset has been done)
+        self.recycles = int(ck.get("recycles", 0))  # (likewise for recycle_dormant: the next recycle's draw)
         # (none before set_horizon existed: the horizon and discount of construction, which `config` has just been compared with)
         self.set_horizon(ck.get("horizon", self.n), ck.get("discount", self._cfg.discount))
 

@@ -18,6 +18,7 @@
 //   learner_internal.h  layout, RB_OPTS, the handle          learner_plan.h     which kernel a shape reaches (pure functions)
 //   head.h / grad_finish.h / adam_kernels.h / noise_kernel.h  kernels           conv_dispatch.h / fc_dispatch.h   the launches
 //   noisy_rows.h  the per-row-noise act layers (kernels)         learn_stats.h  the step records and the held-out loss
+//   param_reset.h  shrink-and-perturb resets                     unit_recycle.h  dormant units: activity, mask, targeted reset
 //   optimizer_host.h / act_host.h / exchange_host.h / layout_api.h / launch_plan_debug.h   the other entry points, by concern
 // Each is included HERE and nowhere else (they define non-template kernels and static functions).
 #include "learner_internal.h"
@@ -33,6 +34,7 @@
 #include "optimizer_host.h"
 #include "param_reset.h"
 #include "learn_stats.h"
+#include "unit_recycle.h"
 #include "act_host.h"
 #include "exchange_host.h"
 #include "layout_api.h"

@@ -45,12 +45,20 @@ def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states,
     agent.reset_parameters(), which restarts t at 0.
     on_log (None: nothing is read, nothing changes): called as on_log(T, agent.read_stats()) right after every learn step whose
     count is a multiple of args.log_interval (in learn steps; absent or 0: never) — the records of the steps since the last call
-    (Agent.track_stats / args.step_stats; None when the agent keeps none).  read_stats synchronises; the steps in between do not."""
+    (Agent.track_stats / args.step_stats; None when the agent keeps none).  read_stats synchronises; the steps in between do not.
+    args.redo_interval (absent or 0: never, no call is made) counts gradient steps like reset_interval: right after the learn step
+    that makes the count a multiple of it, agent.recycle_dormant(mem, tau=args.redo_tau, batches=args.redo_batches (1),
+    target=args.redo_target (False)) recycles the dormant units; where a full reset falls on the same step the reset runs and the
+    recycle is skipped.  With redo_interval in use the records handed to on_log gain `dormant_fraction`, the share the last
+    recycle found (None before the first), read at log time, where the loop synchronises anyway."""
     seed = int(getattr(args, "seed", 0))
     increase = (1 - args.priority_weight) / (T_max - args.learn_start)           # main.py:123
     eval_every = int(getattr(args, "evaluation_interval", 0) or 0)
     replay_ratio = float(getattr(args, "replay_ratio", 0) or 0)                   # learn steps per environment step; may exceed 1
     reset_interval = int(getattr(args, "reset_interval", 0) or 0)                 # in GRADIENT steps; 0 = never
+    redo_interval = int(getattr(args, "redo_interval", 0) or 0)                   # in GRADIENT steps; 0 = never
+    redo_kw = dict(tau=getattr(args, "redo_tau", None), batches=int(getattr(args, "redo_batches", 1) or 1),
+                   target=bool(getattr(args, "redo_target", False)))
     learn_owed, learns = 0.0, 0
     log_interval = int(getattr(args, "log_interval", 0) or 0) if on_log is not None else 0
     n1 = getattr(args, "multi_step_final", None)
@@ -90,13 +98,18 @@ def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states,
                 learns += 1
                 since_reset += 1
                 if log_interval and learns % log_interval == 0:
-                    on_log(T, agent.read_stats())
+                    records = agent.read_stats()
+                    if redo_interval:
+                        records = dict(records or {}, dormant_fraction=agent.dormant_fraction())
+                    on_log(T, records)
                 if reset_interval and learns % reset_interval == 0:
                     agent.reset_parameters()                                      # shrink-and-perturb (Agent.reset_parameters)
                     since_reset = 0
                     if set_horizon is not None:
                         set_horizon(0)                                            # the anneal starts again with the reset
                         horizon_set_at = 0
+                elif redo_interval and learns % redo_interval == 0:
+                    agent.recycle_dormant(mem, **redo_kw)                         # ReDo (Agent.recycle_dormant)
             if on_eval is not None and eval_every and T % eval_every < S:         # main.py:166-170
                 on_eval(T)
                 agent.train()

@@ -17,7 +17,10 @@ the networks every N GRADIENT steps (args.reset_interval: Agent.reset_parameters
 then carries both and the number of resets done.
 `--stats` keeps the device's per-step records (args.step_stats, rainbow_amd/agent_stats.py) and reads them every --log-interval learn
 steps (train_device's on_log): each checkpoint then also shows the means since the checkpoint before it of the loss, the online value
-q, the |target - online| value gap td and the gradient norm g — why a curve moves or does not, not only whether it does."""
+q, the |target - online| value gap td and the gradient norm g — why a curve moves or does not, not only whether it does.
+`--redo N` recycles the dormant units every N GRADIENT steps (args.redo_interval: Agent.recycle_dormant, rainbow_amd/agent_redo.py, tau
+0.1, one batch); the line then carries the number of recycles done, and each checkpoint the dormant share `dorm` the last recycle
+found — beside the `--stats` columns when those are on."""
 import argparse
 import os
 import sys
@@ -43,7 +46,7 @@ def options(t_max, dev, multi_step=20, learn_start=1600, augment_pad=0, target_t
 
 
 def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", multi_step=20, learn_start=1600, augment_pad=0,
-        target_tau=0.0, replay_ratio=0.0, reset_interval=0, stats=False, log_interval=200):
+        target_tau=0.0, replay_ratio=0.0, reset_interval=0, stats=False, log_interval=200, redo=0):
     from rainbow_amd.agent import Agent
     from rainbow_amd.envs import BreakoutVec, CatchVec
     from rainbow_amd.loop import evaluate_device, evaluate_vec, train_device
@@ -54,6 +57,8 @@ def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", mul
     args.seed = seed
     if stats and learn:
         args.step_stats, args.log_interval = 4 * log_interval, log_interval
+    if redo and learn:
+        args.redo_interval = redo
     np.random.seed(seed)
     torch.manual_seed(np.random.randint(1, 10000))
     env = make(S, dev, seed=seed)
@@ -67,11 +72,15 @@ def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", mul
     dropped = [0]
 
     def on_log(T, records):
-        for k in seen:
+        for k in seen:                                                           # (with --redo the records also carry dormant_fraction)
             seen[k].append(records[k])
         dropped[0] += records["dropped"]
 
     def stats_columns():
+        dorm = agent.dormant_fraction() if redo and learn else None              # (reads the last recycle's counts: on_eval may synchronise)
+        return stats_only() + ("[dorm %.3f]" % dorm if dorm is not None else "")
+
+    def stats_only():
         if not (stats and learn) or not seen["loss_mean"]:
             return ""
         m = {k: float(np.nanmean(np.concatenate(v))) for k, v in seen.items()}
@@ -98,6 +107,8 @@ def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", mul
     tag = "learn" if learn else "NO-LEARN"
     if replay_ratio or reset_interval:
         tag += " replay-ratio %g reset-interval %d (%d resets)" % (replay_ratio or 1.0, reset_interval, agent.resets)
+    if redo and learn:
+        tag += " redo-interval %d (%d recycles)" % (redo, agent.recycles)
     print("S %2d seed %3d %s (%.1f s): " % (S, seed, tag, time.perf_counter() - t0)
           + " ".join("%d:%+.3f%s" % c for c in curve) + ("  (%d records dropped)" % dropped[0] if dropped[0] else "") + "  training-episode mean %+.3f" % env.stats()["mean_return"] + note,
           flush=True)
@@ -121,6 +132,7 @@ def main():
     ap.add_argument("--reset-interval", type=int, default=0)
     ap.add_argument("--stats", action="store_true")
     ap.add_argument("--log-interval", type=int, default=200)
+    ap.add_argument("--redo", type=int, default=0, metavar="N")
     a = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
@@ -128,7 +140,7 @@ def main():
     for S in a.streams:
         for k in range(a.seeds if S == 1 else min(3, a.seeds)):
             run(S, 101 + 7 * k, a.t_max, a.t_eval, not a.no_learn, dev, a.protocol, a.env, a.multi_step, a.learn_start, a.augment_pad,
-                a.target_tau, a.replay_ratio, a.reset_interval, a.stats, a.log_interval)
+                a.target_tau, a.replay_ratio, a.reset_interval, a.stats, a.log_interval, a.redo)
 
 
 if __name__ == "__main__":
