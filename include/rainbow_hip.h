@@ -958,6 +958,50 @@ int rb_learner_dormant_mask(rb_learner_t* l, const double* activity_dev, double 
 int rb_learner_recycle_units(rb_learner_t* l, const uint8_t* mask_dev, float noisy_std, uint64_t seed, uint64_t draw,
                              int32_t with_target, float* exp_avg_dev, float* exp_avg_sq_dev, rb_stream_t stream);
 
+/* ---- feature rank (srank: Kumar, Agarwal, Ghosh, Levine, ICLR 2021; feature rank: Lyle, Rowland, Dabney, ICLR 2022) and per-tensor
+ * norms: the two loss-of-plasticity diagnostics beside the dormant-unit share.  Never on the per-step path: a run that does not call
+ * these launches what it launched before.
+ *
+ * The features of a state: RB_FEATURES_HIDDEN, the post-ReLU row [fc_h_v | fc_h_a], d = 2 * hidden; RB_FEATURES_CONV, the last conv
+ * layer's post-ReLU output flattened, d = F (what fc_h reads).  rb_learner_feature_dim: *d of a configuration; no device needed. */
+#define RB_FEATURES_HIDDEN 0
+#define RB_FEATURES_CONV 1
+int rb_learner_feature_dim(const rb_learner_config_t* cfg, int32_t which, int32_t* d);
+
+/* The ONLINE network's forward in eval mode on B = cfg.batch states u8 [B][history][84][84] — the forward of
+ * rb_learner_unit_activity: noise zero, no target rows, no head — then a copy in stream order, nothing synchronises:
+ *   out_dev[b * ld + k] = feature k of row b,   k < d, b < B      float, ld >= d floats between rows
+ * Columns [d, ld) of every row are not written.  The rows are bit-equal to what rb_learner_debug_read hands out after the same
+ * forward (selector 5; selector 6 + nconv - 1).  State rules of rb_learner_unit_activity: a pending optimiser pass runs first;
+ * RB_ERR_STATE while the last learn call's gradients wait for rb_learner_finish_grads or for the fused optimiser pass (the call
+ * overwrites that call's activations); parameters, target, moments, gradients and their norm partials, both noise buffers and the
+ * noise epoch, the step counter and the priority sink's tree are unchanged, bit for bit.                                        */
+int rb_learner_features(rb_learner_t* l, const uint8_t* states_dev, int32_t which, float* out_dev, int32_t ld, rb_stream_t stream);
+
+/* The sample-side Gram matrix of n feature rows, ONE launch, no handle:
+ *   gram_dev[i * n + j] = sum_k phi[i * ld + k] * phi[j * ld + k],  k < d        double [n][n], every element written
+ * phi_dev: float, n rows of ld floats (all n * ld are addressable).  The inputs are widened exactly and the sum is accumulated in
+ * double by v_mfma_f64_16x16x4_f64 (an f32 accumulation leaves a noise floor of sigma_max sqrt(d 2^-24) under the singular values;
+ * here it is sigma_max sqrt(d 2^-53)).  One workgroup per 64 x 64 tile pair of the upper triangle; an off-diagonal value is computed
+ * once and stored at [i][j] and [j][i]: K is symmetric bit for bit.  The reduction over k is never split: every element is one
+ * chain in ascending k, four per MFMA, so the result depends on d alone — not on n, on the grid or on ld; a repeated call is
+ * bit-identical and the K of the first m rows is the top-left block of the K of all of them.  Columns [d, ld) and whatever lies
+ * behind row n - 1 never enter a sum (they may hold NaN).  |K - K_exact| <= d 2^-53 sum_k |phi_ik| |phi_jk|.
+ * RB_ERR_INVALID naming the argument, nothing launched: n outside [1, 4096], d < 1, ld < d, ld % 4 != 0, phi_dev not 16-byte or
+ * gram_dev not 8-byte aligned, 4 * n * ld >= 2^31.                                                                               */
+int rb_gram_f64(const float* phi_dev, int32_t n, int32_t d, int32_t ld, double* gram_dev, rb_stream_t stream);
+
+/* Per tensor of rb_learner_param_layout, in its order (n_tensors = 2 * nconv + 16), over flat buffers shaped like the parameters
+ * (the parameters, the target, the gradient, a moment buffer; 16-byte aligned):
+ *   out_dev[3 * t + 0] = sum a^2    out_dev[3 * t + 1] = sum (a - b)^2  (0 when b_dev is NULL)    out_dev[3 * t + 2] = max |a|
+ * double [n_tensors][3], accumulated in double in a fixed order (a repeated call is bit-identical); a NaN anywhere in a tensor (a or
+ * b) makes all three of ITS values NaN and touches no other tensor; the alignment padding between tensors is never read.  A pending
+ * optimiser pass runs first; with a_dev or b_dev = grads_dev an implicit sigma gradient is materialised first, and the call is
+ * RB_ERR_STATE while the hidden layer's weight gradient is left to the fused optimiser pass.  TWO launches in stream order (partials
+ * of fixed 4096-element chunks; one workgroup per tensor folds them in index order); nothing synchronises, except that a handle's
+ * first call allocates the partials' scratch.                                                                                   */
+int rb_learner_tensor_norms(rb_learner_t* l, const float* a_dev, const float* b_dev, double* out_dev, rb_stream_t stream);
+
 /* White-box access for parity tests: copies an internal activation to out_dev.
  * what: 0 log_ps_a [B][atoms], 1 m (projected target) [B][atoms], 2 argmax a* i32[B],
  *       3 pns_a [B][atoms], 4 logits [3B][atoms*(actions+1)],

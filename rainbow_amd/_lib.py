@@ -211,6 +211,10 @@ SIGNATURES = {
     "rb_learner_unit_activity": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "rb_learner_dormant_mask": (c_int, [c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rb_learner_recycle_units": (c_int, [c_void_p, c_void_p, c_float, c_uint64, c_uint64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "rb_learner_feature_dim": (c_int, [C.POINTER(LearnerConfig), c_int32, C.POINTER(c_int32)]),
+    "rb_learner_features": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
+    "rb_gram_f64": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "rb_learner_tensor_norms": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

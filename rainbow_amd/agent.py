@@ -20,7 +20,8 @@ initialised.
 
 This module: construction, the mode flags, the parameter-space properties and operations, and the noise state.  The learn step
 is agent_learn.py, the act / evaluate paths agent_act.py, state_dict and checkpoints agent_state.py, the step records and the
-held-out loss agent_stats.py, the dormant-unit diagnostic and recycling agent_redo.py; the flat layout, its initial distributions and the optimiser are params.py.
+held-out loss agent_stats.py, the dormant-unit diagnostic and recycling agent_redo.py, the feature rank and the per-tensor norms
+agent_rank.py; the flat layout, its initial distributions and the optimiser are params.py.
 """
 import ctypes as C
 import os
@@ -33,13 +34,14 @@ from . import dist as rdist
 from ._util import current_stream_handle, u64_pair
 from .agent_act import AgentAct
 from .agent_learn import AgentLearn
+from .agent_rank import AgentRank
 from .agent_state import AgentState
 from .agent_redo import AgentRedo
 from .agent_stats import AgentStats
 from .params import _FlatAdam, _query_layout, init_parameters_flat
 
 
-class Agent(AgentLearn, AgentAct, AgentState, AgentStats, AgentRedo):
+class Agent(AgentLearn, AgentAct, AgentState, AgentStats, AgentRedo, AgentRank):
     _h = None                  # (so that __del__ is safe on an object whose construction failed early)
 
     def __init__(self, args, env):

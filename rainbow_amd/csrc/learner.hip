@@ -19,6 +19,7 @@
 //   head.h / grad_finish.h / adam_kernels.h / noise_kernel.h  kernels           conv_dispatch.h / fc_dispatch.h   the launches
 //   noisy_rows.h  the per-row-noise act layers (kernels)         learn_stats.h  the step records and the held-out loss
 //   param_reset.h  shrink-and-perturb resets                     unit_recycle.h  dormant units: activity, mask, targeted reset
+//   feature_gram.h  feature capture and the f64 Gram matrix      tensor_norms.h  per-tensor norms of a flat buffer
 //   optimizer_host.h / act_host.h / exchange_host.h / layout_api.h / launch_plan_debug.h   the other entry points, by concern
 // Each is included HERE and nowhere else (they define non-template kernels and static functions).
 #include "learner_internal.h"
@@ -35,6 +36,8 @@
 #include "param_reset.h"
 #include "learn_stats.h"
 #include "unit_recycle.h"
+#include "feature_gram.h"
+#include "tensor_norms.h"
 #include "act_host.h"
 #include "exchange_host.h"
 #include "layout_api.h"
@@ -90,6 +93,7 @@ int rb_learner_destroy(rb_learner_t* l) {
   if (l->stats_rows) rb_dev_free(l->stats_rows);
   if (l->stats_ticket) rb_dev_free(l->stats_ticket);
   if (l->ones) rb_dev_free(l->ones);
+  tensor_norms_release(l);
   delete l;
   return RB_OK;
 }

@@ -409,3 +409,24 @@ __device__ __forceinline__ double rb_wave_sum_f64(double v) {
   for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
   return v;
 }
+
+// v_mfma_f64_16x16x4_f64: D(16x16) += A(16x4) * B(4x16) in double.  Lane l supplies A[l&15][l>>4] and B[l>>4][l&15] (one f64 each,
+// as the f32 16x16x4 form); the C/D map is NOT the f32 one: D[r] sits at row (l>>4) + 4*r, col l&15.  The interpreter's branch is
+// written here (tests/hipemu has no f64 form): every element one fma chain over k = 0 .. 3 in ascending order.
+typedef double rb_f64x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ rb_f64x4 rb_mfma16_f64(double a, double b, rb_f64x4 c) {
+#if defined(RB_HOST_INTERP)
+  const int lane = rb_lane();
+  double bk[4];
+  for (int k = 0; k < 4; ++k) bk[k] = __shfl(b, (lane & 15) + 16 * k, 64);
+  for (int r = 0; r < 4; ++r) {
+    double acc = c[r];
+    for (int k = 0; k < 4; ++k) acc = fma(__shfl(a, (lane >> 4) + 4 * r + 16 * k, 64), bk[k], acc);
+    c[r] = acc;
+  }
+  return c;
+#else
+  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+#endif
+}
+__device__ __forceinline__ int rb_mfma16_f64_row(int reg, int lane) { return (lane >> 4) + 4 * reg; }

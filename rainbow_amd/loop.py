@@ -50,7 +50,13 @@ def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states,
     that makes the count a multiple of it, agent.recycle_dormant(mem, tau=args.redo_tau, batches=args.redo_batches (1),
     target=args.redo_target (False)) recycles the dormant units; where a full reset falls on the same step the reset runs and the
     recycle is skipped.  With redo_interval in use the records handed to on_log gain `dormant_fraction`, the share the last
-    recycle found (None before the first), read at log time, where the loop synchronises anyway."""
+    recycle found (None before the first), read at log time, where the loop synchronises anyway.
+    args.rank_interval (absent or 0: never, no call is made) counts gradient steps too: right after the learn step that makes the
+    count a multiple of it — before on_log, and before a reset or a recycle that falls on the same step, whose need it is there to
+    show — agent.feature_rank(mem, batches=args.rank_batches (8), layer=args.rank_layer ("hidden")) measures the rank of the
+    features.  It SYNCHRONISES (it copies the Gram matrix to the host and takes its eigenvalues there): keep the interval in the
+    thousands.  With rank_interval in use on_log's records gain `srank`, `feature_rank` and `effective_rank` of the last
+    measurement (None before the first)."""
     seed = int(getattr(args, "seed", 0))
     increase = (1 - args.priority_weight) / (T_max - args.learn_start)           # main.py:123
     eval_every = int(getattr(args, "evaluation_interval", 0) or 0)
@@ -59,6 +65,9 @@ def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states,
     redo_interval = int(getattr(args, "redo_interval", 0) or 0)                   # in GRADIENT steps; 0 = never
     redo_kw = dict(tau=getattr(args, "redo_tau", None), batches=int(getattr(args, "redo_batches", 1) or 1),
                    target=bool(getattr(args, "redo_target", False)))
+    rank_interval = int(getattr(args, "rank_interval", 0) or 0)                   # in GRADIENT steps; 0 = never
+    rank_kw = dict(batches=int(getattr(args, "rank_batches", 8) or 8), layer=getattr(args, "rank_layer", None) or "hidden")
+    rank_last = None
     learn_owed, learns = 0.0, 0
     log_interval = int(getattr(args, "log_interval", 0) or 0) if on_log is not None else 0
     n1 = getattr(args, "multi_step_final", None)
@@ -97,10 +106,15 @@ def _train_rounds(agent, mem, S, args, T_max, on_eval, per_stream_noise, states,
                 learn_owed -= 1
                 learns += 1
                 since_reset += 1
+                if rank_interval and learns % rank_interval == 0:
+                    rank_last = agent.feature_rank(mem, **rank_kw)                # srank & co (Agent.feature_rank); synchronises
                 if log_interval and learns % log_interval == 0:
                     records = agent.read_stats()
                     if redo_interval:
                         records = dict(records or {}, dormant_fraction=agent.dormant_fraction())
+                    if rank_interval:
+                        records = dict(records or {}, **{k: None if rank_last is None else rank_last[k]
+                                                         for k in ("srank", "feature_rank", "effective_rank")})
                     on_log(T, records)
                 if reset_interval and learns % reset_interval == 0:
                     agent.reset_parameters()                                      # shrink-and-perturb (Agent.reset_parameters)

@@ -20,7 +20,10 @@ steps (train_device's on_log): each checkpoint then also shows the means since t
 q, the |target - online| value gap td and the gradient norm g — why a curve moves or does not, not only whether it does.
 `--redo N` recycles the dormant units every N GRADIENT steps (args.redo_interval: Agent.recycle_dormant, rainbow_amd/agent_redo.py, tau
 0.1, one batch); the line then carries the number of recycles done, and each checkpoint the dormant share `dorm` the last recycle
-found — beside the `--stats` columns when those are on."""
+found — beside the `--stats` columns when those are on.
+`--rank N` measures the rank of the hidden features every N GRADIENT steps (args.rank_interval: Agent.feature_rank,
+rainbow_amd/agent_rank.py, 8 batches; it synchronises); each checkpoint then shows the last measurement as `srank` / its feature
+rank / its effective rank, beside the `--stats` and `--redo` columns."""
 import argparse
 import os
 import sys
@@ -46,7 +49,7 @@ def options(t_max, dev, multi_step=20, learn_start=1600, augment_pad=0, target_t
 
 
 def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", multi_step=20, learn_start=1600, augment_pad=0,
-        target_tau=0.0, replay_ratio=0.0, reset_interval=0, stats=False, log_interval=200, redo=0):
+        target_tau=0.0, replay_ratio=0.0, reset_interval=0, stats=False, log_interval=200, redo=0, rank=0):
     from rainbow_amd.agent import Agent
     from rainbow_amd.envs import BreakoutVec, CatchVec
     from rainbow_amd.loop import evaluate_device, evaluate_vec, train_device
@@ -59,6 +62,8 @@ def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", mul
         args.step_stats, args.log_interval = 4 * log_interval, log_interval
     if redo and learn:
         args.redo_interval = redo
+    if rank and learn:
+        args.rank_interval = rank
     np.random.seed(seed)
     torch.manual_seed(np.random.randint(1, 10000))
     env = make(S, dev, seed=seed)
@@ -78,7 +83,10 @@ def run(S, seed, t_max, t_eval, learn, dev, protocol="device", game="catch", mul
 
     def stats_columns():
         dorm = agent.dormant_fraction() if redo and learn else None              # (reads the last recycle's counts: on_eval may synchronise)
-        return stats_only() + ("[dorm %.3f]" % dorm if dorm is not None else "")
+        fr = agent.last_feature_rank if rank and learn else None                 # (the last measurement's dict: host values)
+        return (stats_only() + ("[dorm %.3f]" % dorm if dorm is not None else "")
+                + ("[srank %d rank %d erank %.1f]" % (fr["srank"], fr["feature_rank"], fr["effective_rank"])
+                   if fr is not None and fr["finite"] else ""))
 
     def stats_only():
         if not (stats and learn) or not seen["loss_mean"]:
@@ -133,6 +141,7 @@ def main():
     ap.add_argument("--stats", action="store_true")
     ap.add_argument("--log-interval", type=int, default=200)
     ap.add_argument("--redo", type=int, default=0, metavar="N")
+    ap.add_argument("--rank", type=int, default=0, metavar="N")
     a = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
@@ -140,7 +149,7 @@ def main():
     for S in a.streams:
         for k in range(a.seeds if S == 1 else min(3, a.seeds)):
             run(S, 101 + 7 * k, a.t_max, a.t_eval, not a.no_learn, dev, a.protocol, a.env, a.multi_step, a.learn_start, a.augment_pad,
-                a.target_tau, a.replay_ratio, a.reset_interval, a.stats, a.log_interval, a.redo)
+                a.target_tau, a.replay_ratio, a.reset_interval, a.stats, a.log_interval, a.redo, a.rank)
 
 
 if __name__ == "__main__":
